@@ -10,6 +10,17 @@ collective: weak scaling); the only collectives are the RCCL broadcast of the
 LUT lattice at start-up and a MAX all-reduce of the elapsed time.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B]
+                  [--dump-outputs DIR] [--full]
+A plain run does what the headline needs and no more: set-up, W warm-up
+launches, the K timed ones, the result line.  --full adds every secondary
+measurement to the line (uniform and real content, the host-buffer path, the
+other BASELINE configurations, the sharded C4 / C5 lines, the CPU baseline);
+--no-alt, --no-sharded and --cpu-seconds 0 drop parts of it again.
+--dump-outputs DIR writes what the last timed launch left in the caller's
+output batch to DIR/sdr.npy (float32; DIR/sdr_rank<r>.npy on ranks r > 0):
+the whole [frames, samples] batch when it fits DUMP_MAX_SAMPLES, else a fixed
+seeded sample of its flattened samples.  The inputs are seeded, so two builds
+run with the same arguments can be compared sample for sample.
 For N > 1 the driver launches one process per GPU with torch.distributed.run;
 a plain ``python bench.py --gpus N`` (no WORLD_SIZE in the environment)
 starts that launcher itself, as a child process, before touching the GPU.
@@ -53,10 +64,16 @@ def parse_args():
     ap.add_argument('--pipeline', default='auto', help='auto | cpu | libplacebo (profiling runs of one chain)')
     ap.add_argument('--lp-tone', default='ipt', help='libplacebo branch tone form: ipt | max-rgb')
     ap.add_argument('--peak-detect', action='store_true', help='dynamic peak (profiling runs of C3_dyn)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU-baseline budget (0 = skip)')
-    ap.add_argument('--no-alt', action='store_true', help='skip the uniform-content secondary run')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: uniform / real content, host path, '
+                         'other configurations, sharded C4 / C5, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed launch's output batch (or a seeded sample of it) to DIR/sdr.npy")
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='with --full: CPU-baseline budget (0 = skip)')
+    ap.add_argument('--no-alt', action='store_true',
+                    help='with --full: skip the secondary runs (uniform / real content, host path, other configurations)')
     ap.add_argument('--no-sharded', action='store_true',
-                    help='skip the sharded C4 / C5 lines (profiling runs of the headline kernel alone)')
+                    help='with --full: skip the sharded C4 / C5 lines (profiling runs of the headline kernel alone)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launch + collectives only, no GPU work (CPU test of the multi-rank flow)')
     return ap.parse_args()
@@ -75,6 +92,11 @@ SHARDED = (
      dict(tonemapper='hable', gamma=1.0, bits_in=12, bits_out=12, transfer='arib-std-b67'), 7680, 4320, 16, 65),
 )
 SHARDED_STEPS = 100
+
+# --dump-outputs: at most 8 Mi samples (32 MB of float32); a larger batch is
+# sampled at DUMP_MAX_SAMPLES sorted positions drawn once from DUMP_SEED
+DUMP_MAX_SAMPLES = 1 << 23
+DUMP_SEED = 0x5D12
 
 
 def _free_port() -> int:
@@ -185,6 +207,23 @@ def pmc_traffic(workload):
     return None
 
 
+def dump_outputs(out_dir, buf, rank):
+    """--dump-outputs: the output batch as the caller holds it after the last
+    timed launch ([frames, samples] integer codes), as float32.  A batch above
+    DUMP_MAX_SAMPLES is sampled at sorted positions of its flattened samples,
+    drawn from DUMP_SEED (the same positions for the same shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = buf.numel()
+    if total <= DUMP_MAX_SAMPLES:
+        out = buf.to(torch.float32).cpu().numpy()
+    else:
+        idx = np.sort(np.random.RandomState(DUMP_SEED).randint(0, total, size=DUMP_MAX_SAMPLES, dtype=np.int64))
+        out = buf.reshape(-1)[torch.from_numpy(idx).to(buf.device)].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, 'sdr.npy' if rank == 0 else f'sdr_rank{rank}.npy'), out)
+
+
 def dry_run(args, world, rank):
     """The multi-rank flow without the GPU: gloo process group, the
     params + lattice broadcast, the SUM / MAX reduction; rank 0 prints the
@@ -209,7 +248,7 @@ def dry_run(args, world, rank):
         px, cks, el = reduce_run(px, cks, el)
     # the sharded C4 / C5 lines: same shard and reduction flow, no GPU work
     sharded = {}
-    for tag, workload, kw, w_, h_, fpr, _ in SHARDED:
+    for tag, workload, kw, w_, h_, fpr, _ in (SHARDED if args.full and not args.no_sharded else ()):
         a_, b_ = shard_range(world * fpr, world, rank)
         px_, _, el_ = (b_ - a_) * w_ * h_, 0, 0.001 * (rank + 1)
         if world > 1:
@@ -271,7 +310,9 @@ def main():
     tm = hdr2sdr.Tonemapper(local, params, lattice_host)
     W, H, B = args.width, args.height, args.frames
 
-    def run(kind, make_src=None):
+    alt_on = args.full and not args.no_alt
+
+    def run(kind, make_src=None, dump_dir=None):
         # this rank's frames: global indices [rank*B, rank*B + B) of a
         # world*B-frame sequence (shard_range), synthesised in place
         a, b = shard_range(world * B, world, rank)
@@ -296,6 +337,8 @@ def main():
         tm.set_timing(False)
         px = (b - a) * W * H * args.steps
         cks = frame_checksum(dst.buf, a)
+        if dump_dir:
+            dump_outputs(dump_dir, dst.buf, rank)
         if world > 1:
             px, cks, el = reduce_run(px, cks, el, dev)
         del src, dst
@@ -306,19 +349,20 @@ def main():
         import numpy as np
         from hdr2sdr.synth import frames_from_rgb8
         rgb8w = np.load(real_npz)['hdr']
-        el, kms, px_total, checksum = run('website', lambda n: frames_from_rgb8(rgb8w, n, args.bits_in, dev))
+        el, kms, px_total, checksum = run('website', lambda n: frames_from_rgb8(rgb8w, n, args.bits_in, dev),
+                                            args.dump_outputs)
         del rgb8w
     else:
-        el, kms, px_total, checksum = run(args.kind)
+        el, kms, px_total, checksum = run(args.kind, dump_dir=args.dump_outputs)
     alt = None
-    if not args.no_alt:
+    if alt_on:
         el_u, kms_u, px_u, _ = run('uniform')
         alt = {'kind': 'uniform', 'value': round(px_u / el_u / 1e6, 1), 'kernel_ms': round(kms_u, 4)}
 
     # real content: the reference's own website HDR frame (a 4K capture of PQ
     # BT.2020 R'G'B', tests/golden/website_hdr_full.npz), repeated per frame
     real = None
-    if world == 1 and not args.no_alt and os.path.exists(real_npz) and (W, H) == (3840, 2160):
+    if world == 1 and alt_on and os.path.exists(real_npz) and (W, H) == (3840, 2160):
         import numpy as np
         from hdr2sdr.synth import frames_from_rgb8
         rgb8 = np.load(real_npz)['hdr']
@@ -331,7 +375,7 @@ def main():
     # h2s_process host path: H2D, kernel, D2H): what the drop-in planner's
     # pipes see.  Reported beside, never as, the headline value.
     host_path = None
-    if world == 1 and not args.no_alt:
+    if world == 1 and alt_on:
         hs = synth_frames('smooth' if args.kind == 'website' else args.kind, B, W, H, args.bits_in, device='cpu',
                           seed=0x5EED).to_numpy()
         hsrc = hdr2sdr.FrameBatch.empty_pinned(B, W, H, args.bits_in)
@@ -364,7 +408,7 @@ def main():
     # the other BASELINE.json configurations, single-GPU, for reference
     # (not the headline value): kernel time on device-resident frames
     other = None
-    if world == 1 and not args.no_alt:
+    if world == 1 and alt_on:
         other = {}
         for tag, kw, w_, h_, nf, lut_n in (
                 ('C1', dict(tonemapper='reinhard', gamma=1.0, bits_out=8), 1920, 1080, 16, 33),
@@ -435,7 +479,7 @@ def main():
     # rank exactly as the headline (barrier + synchronize around the timed
     # launches, MAX of the elapsed time over ranks, SUM of pixels)
     sharded = {}
-    for tag, workload, kw, w_, h_, fpr, lut_n in (() if args.no_sharded else SHARDED):
+    for tag, workload, kw, w_, h_, fpr, lut_n in (SHARDED if args.full and not args.no_sharded else ()):
         p_ = hdr2sdr.TonemapParams(mode=args.mode, **kw)
         lat_ = hdr2sdr.generate_lattice(lut_n) if rank == 0 else None
         if world > 1:
@@ -559,7 +603,7 @@ def main():
                    tr.get('valu_issue_frac', float('nan')), tr.get('valu_insts_per_cu_cycle', float('nan')),
                    rec['roofline']['frac']))
     rec['config']['output_checksum'] = checksum
-    if world == 1 and args.cpu_seconds > 0:
+    if world == 1 and args.full and args.cpu_seconds > 0:
         rec['cpu_baseline'] = cpu_baseline(params, lattice_host, W, H, args.cpu_seconds)
     print(json.dumps(rec), flush=True)
     tm.close()

@@ -9,7 +9,7 @@ for lib in "$@"; do
   name=$(basename "$lib" .so)
   OUT=$ROOT/gpurun_out/clk_$name; mkdir -p "$OUT"
   (cd /tmp && H2S_LIB=$ROOT/$lib timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES -d "$OUT" -o run \
-     --output-format csv -- python3 "$ROOT/bench.py" --steps 6 --warmup 1 --cpu-seconds 0 --no-alt > "$OUT/bench.log" 2>&1) \
+     --output-format csv -- python3 "$ROOT/bench.py" --full --steps 6 --warmup 1 --cpu-seconds 0 --no-alt > "$OUT/bench.log" 2>&1) \
     || { echo "$name failed"; tail -3 "$OUT/bench.log"; exit 1; }
   python3 - "$OUT" "$name" <<'PY'
 import collections, csv, glob, json, sys

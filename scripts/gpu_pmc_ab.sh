@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   n=$(basename "$lib" .so)
-  H2S_LIB=$R/$lib timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_CVT SQ_WAVES -d "$OUT/$n" -o run --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-alt --cpu-seconds 0 --tonemapper bt.2390 --gamma 1.0 --pipeline libplacebo > "$OUT/$n.log" 2>&1 || { tail -5 "$OUT/$n.log"; exit 1; }
+  H2S_LIB=$R/$lib timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_CVT SQ_WAVES -d "$OUT/$n" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-alt --cpu-seconds 0 --tonemapper bt.2390 --gamma 1.0 --pipeline libplacebo > "$OUT/$n.log" 2>&1 || { tail -5 "$OUT/$n.log"; exit 1; }
   f=$(find "$OUT/$n" -name "*counter_collection.csv" -print -quit)
   python3 - "$f" "$n" <<'PY'
 import csv, sys, collections

@@ -24,6 +24,6 @@ for d in "$@"; do
   tail -4 "$OUT/$(basename $d .py).log"
 done
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log" | cut -c1-600
 fi

@@ -14,6 +14,6 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('s
   || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
 echo "=== bench"
-timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 cut -c1-300 "$OUT/bench.json"

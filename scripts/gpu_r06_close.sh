@@ -23,7 +23,7 @@ if [ "${PART:-A}" = A ]; then
     || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
   tail -1 "$OUT/smoke.log"
   echo "=== bench"
-  timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log" > "$OUT/bench.json"
   cut -c1-300 "$OUT/bench.json"
   echo "=== peak statistics trace"

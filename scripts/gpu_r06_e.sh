@@ -27,6 +27,6 @@ rc=$?
 tail -5 "$OUT/pytest_gpu.log"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "pytest rc=$rc"; exit $rc; }
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log" | cut -c1-400
 fi

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 BENCH=0 bash scripts/gpu_r06_e.sh "$TAG" scripts/variants/libh2s_r06a.so || exit $?
-timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log" | cut -c1-300
 timeout -k 10 200 python -u scripts/bench_peak_stats.py > "$OUT/bench_peak.log" 2>&1 || { tail -5 "$OUT/bench_peak.log"; exit 1; }
 tail -1 "$OUT/bench_peak.log"

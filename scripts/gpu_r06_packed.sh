@@ -13,7 +13,7 @@ timeout -k 10 400 env H2S_LIB=$V python -u -m pytest tests/test_00_gpu_baseline.
   --timeout 200 --timeout-method thread -k "not libplacebo and not lp_exact and not C3 and not spline and not bt2390" \
   > "$OUT/pytest_packed.log" 2>&1 || { tail -30 "$OUT/pytest_packed.log"; exit 1; }
 tail -2 "$OUT/pytest_packed.log"
-A="--steps 300 --warmup 10 --cpu-seconds 0"
+A="--full --steps 300 --warmup 10 --cpu-seconds 0"
 for r in 1 2; do
   for lib in product packed; do
     L=""; [ $lib = packed ] && L="H2S_LIB=$V"

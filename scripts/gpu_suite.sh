@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU call: the -m gpu suite (float-stage report to $OUT/float_report.jsonl),
-# then the default bench line.  Each GPU step under its own limit; stop at the
+# then the full bench line.  Each GPU step under its own limit; stop at the
 # first failure.  Usage: scripts/gpu_suite.sh TAG [pytest-args...]
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -17,5 +17,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu ${PYTEST_STOP:--x} -q --timeo
 rc=$?
 tail -3 "$OUT/pytest_gpu.log"
 [ $rc -eq 0 ] || { echo "pytest rc=$rc"; exit $rc; }
-timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -5 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"

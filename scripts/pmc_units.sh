@@ -6,7 +6,7 @@ LIB=$1; TAG=$2
 OUT=$ROOT/gpurun_out/pmc_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp H2S_LIB=$ROOT/$LIB
 cd /tmp
-ARGS="--steps 4 --warmup 1 --cpu-seconds 0 --no-alt"
+ARGS="--full --steps 4 --warmup 1 --cpu-seconds 0 --no-alt"
 i=0
 for set in "TA_TA_BUSY_sum TA_BUFFER_TOTAL_CYCLES_sum TD_TD_BUSY_sum TD_TC_STALL_sum GRBM_GUI_ACTIVE" \
            "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum GRBM_GUI_ACTIVE" \

@@ -21,7 +21,7 @@ def _run(args, **env):
 
 
 def test_plain_gpus2_spawns_two_ranks_under_gloo():
-    out = _run(['--gpus', '2', '--dry-run', '--frames', '3'])
+    out = _run(['--gpus', '2', '--dry-run', '--full', '--frames', '3'])
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1                              # rank 0 prints the one line
