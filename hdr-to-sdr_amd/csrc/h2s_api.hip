@@ -38,79 +38,188 @@ hipError_t launch_peak_curves(double2* fstat, int n, const PeakModel& M, PeakSta
 using h2s::FastParams;
 using h2s::KParams;
 
+struct h2s_ctx;
+
 namespace {
 thread_local std::string g_err;  // errors with no context
 constexpr int kEvRing = 256;
 constexpr int kMaxChunks = 8;  // host-frame pipeline depth (chunks per call)
+
+int fail(h2s_ctx* c, int code, const std::string& msg);
+int hip_fail(h2s_ctx* c, hipError_t e, const char* what);
+
+// ---- owners of the context's device resources ----
+
+// device buffer of at least `cap` bytes (grown, never shrunk); a grown
+// buffer is freed only after the launches that read the old one (hipFree
+// synchronises).  pool set (the lattices): a stream-ordered allocation of
+// that stream instead (hipMallocAsync / hipFreeAsync), which must still
+// exist at release
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipStream_t pool = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), pool(o.pool) { o.p = nullptr, o.cap = 0; }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) pool ? hipFreeAsync(p, pool) : hipFree(p);
+    p = nullptr, cap = 0;
+  }
+  int reserve(h2s_ctx* c, size_t bytes, const char* what, bool* grew = nullptr) {
+    if (bytes <= cap) return 0;
+    release();
+    if ((pool ? hipMallocAsync(&p, bytes, pool) : hipMalloc(&p, bytes)) != hipSuccess) {
+      p = nullptr;
+      return fail(c, H2S_E_OOM, std::string(what) + " allocation failed");
+    }
+    cap = bytes;
+    if (grew) *grew = true;
+    return 0;
+  }
+};
+
+template <class T>
+struct Dev : DevBuf {
+  operator T*() const { return static_cast<T*>(p); }
+};
+
+// created on first use: non-blocking streams, and events without timing
+// (the timing ring asks for hipEventDefault)
+struct Stream {
+  hipStream_t s = nullptr;
+  ~Stream() {
+    if (s) hipStreamDestroy(s);
+  }
+  int get(h2s_ctx* c, const char* what) {
+    if (s) return 0;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) return 0;
+    s = nullptr;
+    return hip_fail(c, e, what);
+  }
+};
+
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    std::swap(ev, o.ev);
+    return *this;
+  }
+  ~Event() {
+    if (ev) hipEventDestroy(ev);
+  }
+  int get(h2s_ctx* c, const char* what, unsigned flags = hipEventDisableTiming) {
+    if (ev) return 0;
+    hipError_t e = hipEventCreateWithFlags(&ev, flags);
+    if (e == hipSuccess) return 0;
+    ev = nullptr;
+    return hip_fail(c, e, what);
+  }
+};
+
+// One scratch of the context that calls on different streams share (the
+// BICUBIC plane, the peak buffers and state, a derived lattice while it is
+// built): the call that uses it marks its stream afterwards, and the next
+// call waits on its own stream for that mark before it touches the scratch.
+// The rule for the steady state: once the marked work is seen complete
+// (hipEventQuery in wait) pending is cleared, and from then on the guard
+// makes no HIP call until the next mark
+struct Ordered {
+  Event ev;
+  bool pending = false;
+  int wait(h2s_ctx* c, hipStream_t s, const char* what) {
+    if (!pending) return 0;
+    if (hipEventQuery(ev.ev) == hipSuccess) {
+      pending = false;
+      return 0;
+    }
+    hipError_t e = hipStreamWaitEvent(s, ev.ev, 0);
+    return e == hipSuccess ? 0 : hip_fail(c, e, what);
+  }
+  int mark(h2s_ctx* c, hipStream_t s, const char* what) {
+    if (int rc = ev.get(c, what)) return rc;
+    hipError_t e = hipEventRecord(ev.ev, s);
+    if (e != hipSuccess) return hip_fail(c, e, what);
+    pending = true;
+    return 0;
+  }
+  int sync_host(h2s_ctx* c, const char* what) {
+    if (!pending) return 0;
+    hipError_t e = hipEventSynchronize(ev.ev);
+    if (e != hipSuccess) return hip_fail(c, e, what);
+    pending = false;
+    return 0;
+  }
+};
 }  // namespace
 
-struct h2s_ctx {
+// (hidden: its implicit destructor is no part of the library's symbol set)
+struct __attribute__((visibility("hidden"))) h2s_ctx {
   int device = 0;
   h2s_params params{};
   bool params_set = false;
   KParams k{};  // resolved constants (pointers filled per call)
-  float4* d_lut = nullptr;
+  // set_params / set_lut copy and (re)allocate on this non-blocking stream
+  // (stream-ordered hipMallocAsync / hipFreeAsync for the lattices): no
+  // null-stream copy or hipFree, which would wait for the whole device.
+  // h2s_destroy releases the lattices and waits for the stream before the
+  // members go; declared before them, it would outlive them in any case
+  Stream aux;
+  Dev<float4> d_lut;
   int lut_n = 0;
-  float* d_lut_yuv = nullptr;  // lattice pre-multiplied into output code space (3 floats/point)
+  Dev<float> d_lut_yuv;  // lattice pre-multiplied into output code space (3 floats/point)
   float lut_yuv_scale = -1.0f;  // quantiser scale it was built for (-1 = stale)
   int lut_yuv_rgb = 0;          // 1: it holds plain R'G'B' records (libplacebo rgba8 form)
-  unsigned* d_lut8x = nullptr;  // libplacebo branch: lut3d's 8-bit output per rgba code triple (2^24, 64 MiB)
+  Dev<unsigned> d_lut8x;  // libplacebo branch: lut3d's 8-bit output per rgba code triple (2^24, 64 MiB)
   bool lut8x_ok = false;        // built for the current lattice
+  Ordered lut_built;      // after the last build of d_lut_yuv / d_lut8x (queued on the caller's stream)
   bool fast_enabled = true;
   bool lp_exact = false;  // H2S_OPT_LP_EXACT
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
   int tiles_per_block = 8;  // k_tile: tiles one block walks (H2S_TILES_PER_BLOCK overrides, 1..64)
-  uint16_t* d_eq = nullptr;
-  float4* d_pq = nullptr;  // PQ EOTF cubic segments (fast path)
-  float4* d_hlg = nullptr; // HLG inverse-OETF cubic segments (fast path, CPU chain)
-  float4* d_pqi = nullptr; // PQ inverse EOTF cubic segments (fast path, lp_tone IPT)
-  void* d_stage = nullptr;
-  size_t stage_bytes = 0;
-  void* d_prev = nullptr;  // preview scratch
-  size_t prev_bytes = 0;
+  Dev<uint16_t> d_eq;
+  Dev<float4> d_pq;   // PQ EOTF cubic segments (fast path)
+  Dev<float4> d_hlg;  // HLG inverse-OETF cubic segments (fast path, CPU chain)
+  Dev<float4> d_pqi;  // PQ inverse EOTF cubic segments (fast path, lp_tone IPT)
+  Dev<uint8_t> d_stage;
+  Dev<uint8_t> d_prev;  // preview scratch
   // dynamic peak (params.peak_detect), all on the device: statistics ->
   // per-frame (max, avg) -> IIR + curve records -> conversion, queued on the
   // caller's stream with no host round trip (h2s_peak.h)
-  void* d_stats = nullptr;       // per-block partials, then (percentile model) histograms
+  Dev<float2> d_stats;           // per-block partials, then (percentile model) histograms
   int stats_nf = 0;   // frames d_stats is laid out for (frame_stats)
-  double2* d_fstat = nullptr;    // per frame: the statistic, then the smoothed (max, avg) its curve uses
-  size_t fstat_cap = 0;
-  h2s::CurveConsts* d_curve = nullptr;    // one curve record per frame of a dynamic-peak launch
-  size_t curve_cap = 0;
-  h2s::PeakState* d_pk = nullptr;         // [0] the smoothing state; [1] a preview's saved copy of it
-  hipEvent_t peak_ev = nullptr;           // after the last launch that used the buffers above
-  bool peak_pending = false;
+  Dev<double2> d_fstat;          // per frame: the statistic, then the smoothed (max, avg) its curve uses
+  Dev<h2s::CurveConsts> d_curve; // one curve record per frame of a dynamic-peak launch
+  Dev<h2s::PeakState> d_pk;      // [0] the smoothing state; [1] a preview's saved copy of it
+  Ordered peak_use;              // after the last launch that used the buffers above
   // pipelined schedule (run_dynamic_peak_chunked; private A/B hook
   // H2S_OPT_TEST_PEAK_CHUNK, off: measured slower): frames per
   // chunk (0 = one statistics launch, then one conversion launch, all on the
   // caller's stream), the statistics stream and a second conversion stream,
   // events: start | end | per-chunk statistics
   int peak_chunk = 0;
-  hipStream_t pk_s[2] = {};
-  std::vector<hipEvent_t> pk_ev;
+  Stream pk_s[2];
+  std::vector<Event> pk_ev;
   std::string err;
   bool fail_after_launch = false;  // H2S_OPT_TEST_FAIL_AFTER_LAUNCH (private test hook, one call)
   bool timing = false;
-  hipEvent_t ev0[kEvRing] = {}, ev1[kEvRing] = {};
+  Event ev0[kEvRing], ev1[kEvRing];
   long long ev_count = 0;  // launches recorded since reset
   // host-frame pipeline: H2D, compute and D2H of consecutive chunks on
   // their own streams (two DMA directions overlap the kernel and each other)
-  hipStream_t ps[3] = {};
-  hipEvent_t pev[2 * kMaxChunks + 2] = {};
+  Stream ps[3];
+  Event pev[2 * kMaxChunks + 2];
   // events recorded after this context's own asynchronous launches, on the
   // streams they went to: set_params / set_lut wait for exactly these (no
   // device-wide synchronisation), then recycle them
-  std::vector<hipEvent_t> pend, ev_free;
-  hipEvent_t chr_ev = nullptr;   // after the last BICUBIC two-pass launch (d_chr scratch in use)
-  // set_params / set_lut copy and (re)allocate on this non-blocking stream
-  // (stream-ordered hipMallocAsync / hipFreeAsync for the lattices): no
-  // null-stream copy or hipFree, which would wait for the whole device
-  hipStream_t aux = nullptr;
-  bool chr_pending = false;
-  float2* d_chr = nullptr;       // BICUBIC chroma: one frame's per-pixel (Cb, Cr)
-  size_t chr_cap = 0;
+  std::vector<Event> pend, ev_free;
+  Dev<float2> d_chr;             // BICUBIC chroma: one frame's per-pixel (Cb, Cr)
+  Ordered chr_use;               // after the last BICUBIC two-pass launch (d_chr in use)
 };
 
 namespace {
@@ -670,40 +779,13 @@ void h2s_destroy(h2s_ctx* c) {
   if (!c) return;
   DeviceGuard g(c->device);
   hipDeviceSynchronize();
-  if (c->aux) {  // the lattices are stream-ordered allocations of the context stream
-    if (c->d_lut) hipFreeAsync(c->d_lut, c->aux);
-    if (c->d_lut_yuv) hipFreeAsync(c->d_lut_yuv, c->aux);
-    if (c->d_lut8x) hipFreeAsync(c->d_lut8x, c->aux);
-    hipStreamSynchronize(c->aux);
-    hipStreamDestroy(c->aux);
+  if (c->aux.s) {  // the lattices are stream-ordered allocations of the context stream
+    c->d_lut.release();
+    c->d_lut_yuv.release();
+    c->d_lut8x.release();
+    hipStreamSynchronize(c->aux.s);
   }
-  if (c->d_eq) hipFree(c->d_eq);
-  if (c->d_pq) hipFree(c->d_pq);
-  if (c->d_hlg) hipFree(c->d_hlg);
-  if (c->d_pqi) hipFree(c->d_pqi);
-  if (c->d_stage) hipFree(c->d_stage);
-  if (c->d_prev) hipFree(c->d_prev);
-  if (c->d_stats) hipFree(c->d_stats);
-  if (c->d_fstat) hipFree(c->d_fstat);
-  if (c->d_curve) hipFree(c->d_curve);
-  if (c->d_pk) hipFree(c->d_pk);
-  if (c->d_chr) hipFree(c->d_chr);
-  if (c->peak_ev) hipEventDestroy(c->peak_ev);
-  for (hipEvent_t ev : c->pk_ev) hipEventDestroy(ev);
-  for (hipStream_t ps : c->pk_s)
-    if (ps) hipStreamDestroy(ps);
-  if (c->chr_ev) hipEventDestroy(c->chr_ev);
-  for (hipEvent_t ev : c->pend) hipEventDestroy(ev);
-  for (hipEvent_t ev : c->ev_free) hipEventDestroy(ev);
-  for (int i = 0; i < kEvRing; i++) {
-    if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
-    if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
-  }
-  for (hipEvent_t ev : c->pev)
-    if (ev) hipEventDestroy(ev);
-  for (hipStream_t ps : c->ps)
-    if (ps) hipStreamDestroy(ps);
-  delete c;
+  delete c;  // the members' destructors free the rest, on this device (g is still in scope)
 }
 
 // set_params / set_lut rewrite device tables that this context's queued
@@ -711,32 +793,34 @@ void h2s_destroy(h2s_ctx* c) {
 // launches (include/h2s.h), not for the device
 static int drain_launches(h2s_ctx* c) {
   hipError_t e = hipSuccess;
-  for (hipEvent_t ev : c->pend) {
-    const hipError_t r = hipEventSynchronize(ev);
+  for (Event& ev : c->pend) {
+    const hipError_t r = hipEventSynchronize(ev.ev);
     if (e == hipSuccess) e = r;
-    c->ev_free.push_back(ev);
+    c->ev_free.push_back(std::move(ev));
   }
   c->pend.clear();
   if (e != hipSuccess) return hip_fail(c, e, "draining queued launches");
   return 0;
 }
 
+// the context stream, which is also the lattices' allocation pool
 static int aux_stream(h2s_ctx* c, hipStream_t* out) {
-  if (!c->aux) {
-    hipError_t e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      c->aux = nullptr;
-      return hip_fail(c, e, "table stream");
-    }
-  }
-  *out = c->aux;
+  if (int rc = c->aux.get(c, "table stream")) return rc;
+  *out = c->d_lut.pool = c->d_lut_yuv.pool = c->d_lut8x.pool = c->aux.s;
   return 0;
 }
 
 // host -> device table copy on the context's own stream, waited for there
 static hipError_t table_copy(h2s_ctx* c, void* dst, const void* src, size_t bytes) {
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->aux);
-  return e == hipSuccess ? hipStreamSynchronize(c->aux) : e;
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->aux.s);
+  return e == hipSuccess ? hipStreamSynchronize(c->aux.s) : e;
+}
+
+// a table of the context's: (first use) allocate, then upload
+static int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what) {
+  if (int rc = buf.reserve(c, bytes, what)) return rc;
+  hipError_t e = table_copy(c, buf.p, src, bytes);
+  return e == hipSuccess ? 0 : hip_fail(c, e, (std::string(what) + " upload").c_str());
 }
 
 static int note_launch(h2s_ctx* c, hipStream_t s);
@@ -758,25 +842,23 @@ static int note_launch(h2s_ctx* c, hipStream_t s) {
   if (c->pend.size() >= 32) {   // recycle the events that have completed
     size_t j = 0;
     for (size_t i = 0; i < c->pend.size(); i++) {
-      if (hipEventQuery(c->pend[i]) == hipSuccess) c->ev_free.push_back(c->pend[i]);
-      else c->pend[j++] = c->pend[i];
+      if (hipEventQuery(c->pend[i].ev) == hipSuccess) c->ev_free.push_back(std::move(c->pend[i]));
+      else c->pend[j++] = std::move(c->pend[i]);
     }
     c->pend.resize(j);
   }
-  hipEvent_t ev = nullptr;
+  Event ev;
   if (!c->ev_free.empty()) {
-    ev = c->ev_free.back();
+    ev = std::move(c->ev_free.back());
     c->ev_free.pop_back();
-  } else {
-    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) return hip_fail(c, e, "launch event");
   }
-  hipError_t e = hipEventRecord(ev, s);
+  if (int rc = ev.get(c, "launch event")) return rc;
+  hipError_t e = hipEventRecord(ev.ev, s);
   if (e != hipSuccess) {
-    c->ev_free.push_back(ev);
+    c->ev_free.push_back(std::move(ev));
     return hip_fail(c, e, "launch event");
   }
-  c->pend.push_back(ev);
+  c->pend.push_back(std::move(ev));
   return 0;
 }
 
@@ -792,21 +874,13 @@ int h2s_set_lut(h2s_ctx* c, const float* rgb, int n) {
   if (int rc = aux_stream(c, &aux)) return rc;
   // a size change reallocates stream-ordered on the context's stream: a plain
   // hipFree would wait for every stream on the device
-  if (c->d_lut && c->lut_n != n) {
-    hipFreeAsync(c->d_lut, aux);
-    c->d_lut = nullptr;
-    if (c->d_lut_yuv) hipFreeAsync(c->d_lut_yuv, aux);
-    c->d_lut_yuv = nullptr;
+  if (c->lut_n != n) {
+    c->d_lut.release();
+    c->d_lut_yuv.release();
   }
   c->lut_yuv_scale = -1.0f;
   c->lut8x_ok = false;
-  if (!c->d_lut) {
-    hipError_t e = hipMallocAsync((void**)&c->d_lut, cnt * sizeof(float4), aux);
-    if (e != hipSuccess) {
-      c->d_lut = nullptr;
-      return fail(c, H2S_E_OOM, "LUT device allocation failed");
-    }
-  }
+  if (int rc = c->d_lut.reserve(c, cnt * sizeof(float4), "LUT device")) return rc;
   hipError_t e = table_copy(c, c->d_lut, host.data(), cnt * sizeof(float4));
   if (e != hipSuccess) return hip_fail(c, e, "LUT upload");
   c->lut_n = n;
@@ -825,45 +899,23 @@ int h2s_set_params(h2s_ctx* c, const h2s_params* p) {
   std::vector<uint16_t> eq;
   KParams k;
   resolve(p, &k, &eq);
-  if (!c->d_eq) {
-    hipError_t e = hipMalloc((void**)&c->d_eq, 4096 * sizeof(uint16_t));
-    if (e != hipSuccess) {
-      c->d_eq = nullptr;
-      return fail(c, H2S_E_OOM, "eq table allocation failed");
-    }
-  }
-  hipError_t e = table_copy(c, c->d_eq, eq.data(), eq.size() * sizeof(uint16_t));
-  if (e != hipSuccess) return hip_fail(c, e, "eq table upload");
+  // the eq table is allocated for the deepest quantiser (12 bits)
+  if ((rc = c->d_eq.reserve(c, 4096 * sizeof(uint16_t), "eq table")) ||
+      (rc = upload_table(c, c->d_eq, eq.data(), eq.size() * sizeof(uint16_t), "eq table")))
+    return rc;
   {
-    std::vector<float4> pq;
+    std::vector<float4> tab;
     // (x 10000/npl for either input transfer: the libplacebo branch's IPT form
     // decodes PQ L'M'S' through it for HLG input too)
-    build_pq_table(10000.0 / p->npl, &pq);
-    if (!c->d_pq && (e = hipMalloc((void**)&c->d_pq, pq.size() * sizeof(float4))) != hipSuccess) {
-      c->d_pq = nullptr;
-      return fail(c, H2S_E_OOM, "PQ table allocation failed");
-    }
-    if ((e = table_copy(c, c->d_pq, pq.data(), pq.size() * sizeof(float4))) != hipSuccess)
-      return hip_fail(c, e, "PQ table upload");
+    build_pq_table(10000.0 / p->npl, &tab);
+    if ((rc = upload_table(c, c->d_pq, tab.data(), tab.size() * sizeof(float4), "PQ table"))) return rc;
     if (!c->d_pqi) {
-      std::vector<float4> pqi;
-      build_pqi_table(&pqi);
-      if ((e = hipMalloc((void**)&c->d_pqi, pqi.size() * sizeof(float4))) != hipSuccess) {
-        c->d_pqi = nullptr;
-        return fail(c, H2S_E_OOM, "PQ encode table allocation failed");
-      }
-      if ((e = table_copy(c, c->d_pqi, pqi.data(), pqi.size() * sizeof(float4))) != hipSuccess)
-        return hip_fail(c, e, "PQ encode table upload");
+      build_pqi_table(&tab);
+      if ((rc = upload_table(c, c->d_pqi, tab.data(), tab.size() * sizeof(float4), "PQ encode table"))) return rc;
     }
     if (!c->d_hlg && p->transfer_in == H2S_TRC_HLG) {   // parameter-independent: built once
-      std::vector<float4> hlg;
-      build_hlg_table(&hlg);
-      if ((e = hipMalloc((void**)&c->d_hlg, hlg.size() * sizeof(float4))) != hipSuccess) {
-        c->d_hlg = nullptr;
-        return fail(c, H2S_E_OOM, "HLG table allocation failed");
-      }
-      if ((e = table_copy(c, c->d_hlg, hlg.data(), hlg.size() * sizeof(float4))) != hipSuccess)
-        return hip_fail(c, e, "HLG table upload");
+      build_hlg_table(&tab);
+      if ((rc = upload_table(c, c->d_hlg, tab.data(), tab.size() * sizeof(float4), "HLG table"))) return rc;
     }
   }
   c->params = *p;
@@ -980,39 +1032,45 @@ static void resolve_fast(const h2s_ctx* c, const KParams& k, FastParams* F) {
 // the context stream once, rebuilt on s after every h2s_set_lut
 static int ensure_lut8x(h2s_ctx* c, hipStream_t s) {
   if (c->d_lut8x && c->lut8x_ok) return 0;
-  if (!c->d_lut8x) {
-    hipStream_t aux;
-    if (int rc = aux_stream(c, &aux)) return rc;
-    hipError_t e = hipMallocAsync((void**)&c->d_lut8x, sizeof(unsigned) << 24, aux);
-    if (e == hipSuccess) e = hipStreamSynchronize(aux);
-    if (e != hipSuccess) {
-      c->d_lut8x = nullptr;
-      return fail(c, H2S_E_OOM, "lut3d 8-bit table allocation failed");
-    }
+  hipStream_t aux;
+  bool grew = false;
+  int rc;
+  if ((rc = aux_stream(c, &aux)) || (rc = c->d_lut8x.reserve(c, sizeof(unsigned) << 24, "lut3d 8-bit table", &grew)))
+    return rc;
+  if (grew && hipStreamSynchronize(aux) != hipSuccess) {
+    c->d_lut8x.release();
+    return fail(c, H2S_E_OOM, "lut3d 8-bit table allocation failed");
   }
   hipError_t e = h2s::build_lut8x(c->d_lut, c->lut_n, c->d_lut8x, s);
   if (e != hipSuccess) return hip_fail(c, e, "lut3d 8-bit table build");
+  if ((rc = c->lut_built.mark(c, s, "lut3d 8-bit table build"))) return rc;
   c->lut8x_ok = true;
   return 0;
 }
 
+// the tile kernel's derived lattice is current, and its build (queued on the
+// stream of the call that found it stale) is ordered before this call's use
 static int ensure_lut_yuv(h2s_ctx* c, const KParams& k, hipStream_t s) {
+  int rc;
+  if ((rc = c->lut_built.wait(c, s, "lattice build ordering"))) return rc;
   if (k.rgba8) return ensure_lut8x(c, s);   // the libplacebo branch reads only its 8-bit table
   if (c->d_lut_yuv && c->lut_yuv_scale == k.qscale && c->lut_yuv_rgb == k.rgba8) return 0;
   const size_t cnt = (size_t)c->lut_n * c->lut_n * c->lut_n;
-  if (!c->d_lut_yuv) {  // beside d_lut: stream-ordered on the context stream, complete before s uses it
-    hipStream_t aux;
-    if (int rc = aux_stream(c, &aux)) return rc;
-    // zero-filled tail: a coordinate clamped to exactly N-1 (k_tile's
-    // H2S_EXPCLAMP form) names cell N-1, whose corners past the lattice edge
-    // carry weight 0 but are still read; the scalar-record steps read them
-    // without the buffer resource's bounds check, so they must be mapped
-    const size_t pad = 12 * (1 + (size_t)c->lut_n + (size_t)c->lut_n * c->lut_n) + 16;
-    hipError_t e = hipMallocAsync((void**)&c->d_lut_yuv, cnt * 3 * sizeof(float) + pad, aux);
-    if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)c->d_lut_yuv + cnt * 3 * sizeof(float), 0, pad, aux);
+  // beside d_lut: stream-ordered on the context stream, complete before s uses it.
+  // zero-filled tail: a coordinate clamped to exactly N-1 (k_tile's
+  // H2S_EXPCLAMP form) names cell N-1, whose corners past the lattice edge
+  // carry weight 0 but are still read; the scalar-record steps read them
+  // without the buffer resource's bounds check, so they must be mapped
+  const size_t pad = 12 * (1 + (size_t)c->lut_n + (size_t)c->lut_n * c->lut_n) + 16;
+  hipStream_t aux;
+  bool grew = false;
+  if ((rc = aux_stream(c, &aux)) || (rc = c->d_lut_yuv.reserve(c, cnt * 3 * sizeof(float) + pad, "YUV lattice", &grew)))
+    return rc;
+  if (grew) {
+    hipError_t e = hipMemsetAsync(c->d_lut_yuv + cnt * 3, 0, pad, aux);
     if (e == hipSuccess) e = hipStreamSynchronize(aux);
     if (e != hipSuccess) {
-      c->d_lut_yuv = nullptr;
+      c->d_lut_yuv.release();
       return fail(c, H2S_E_OOM, "YUV lattice allocation failed");
     }
   }
@@ -1022,6 +1080,7 @@ static int ensure_lut_yuv(h2s_ctx* c, const KParams& k, hipStream_t s) {
   for (int i = 0; i < 3; i++) K.k709[i] = k.k709[i], K.kcb[i] = k.kcb[i], K.kcr[i] = k.kcr[i];
   hipError_t e = h2s::build_lut_yuv(c->d_lut, c->d_lut_yuv, c->lut_n, K, s);
   if (e != hipSuccess) return hip_fail(c, e, "YUV lattice build");
+  if ((rc = c->lut_built.mark(c, s, "YUV lattice build"))) return rc;
   c->lut_yuv_scale = k.qscale;
   c->lut_yuv_rgb = k.rgba8;
   return 0;
@@ -1204,16 +1263,7 @@ static int choose_path(const h2s_ctx* c, const KParams& k, const h2s_frames* din
 static int ensure_chr(h2s_ctx* c, const KParams& k) {
   // whole 32-row tiles: k_tile writes the rows of its bottom tile past H
   const size_t need = (size_t)k.W * (size_t)((k.H + h2s::TBH - 1) / h2s::TBH * h2s::TBH);
-  if (need <= c->chr_cap) return 0;
-  if (c->d_chr) hipFree(c->d_chr);
-  c->d_chr = nullptr;
-  c->chr_cap = 0;
-  if (hipMalloc((void**)&c->d_chr, need * sizeof(float2)) != hipSuccess) {
-    c->d_chr = nullptr;
-    return fail(c, H2S_E_OOM, "bicubic chroma scratch allocation failed");
-  }
-  c->chr_cap = need;
-  return 0;
+  return c->d_chr.reserve(c, need * sizeof(float2), "bicubic chroma scratch");
 }
 
 // libplacebo-style detected peak (PARITY UNPINNED; model in DESIGN.md §4.6),
@@ -1238,57 +1288,23 @@ static h2s::PeakModel peak_model(const h2s_ctx* c, const KParams& k) {
   return m;
 }
 
-// device buffer of at least `need` bytes (grown, never shrunk); a grown
-// buffer is freed only after the launches that read the old one (hipFree
-// synchronises)
-static int ensure_dev(h2s_ctx* c, void** buf, size_t* cap, size_t need, const char* what) {
-  if (need <= *cap) return 0;
-  if (*buf) hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  if (hipMalloc(buf, need) != hipSuccess) {
-    *buf = nullptr;
-    return fail(c, H2S_E_OOM, std::string(what) + " allocation failed");
-  }
-  *cap = need;
-  return 0;
-}
-
 static int ensure_peak_state(h2s_ctx* c) {
-  if (c->d_pk) return 0;
-  if (hipMalloc((void**)&c->d_pk, 2 * sizeof(h2s::PeakState)) != hipSuccess) {
-    c->d_pk = nullptr;
-    return fail(c, H2S_E_OOM, "peak state allocation failed");
-  }
+  bool grew = false;
+  int rc = c->d_pk.reserve(c, 2 * sizeof(h2s::PeakState), "peak state", &grew);
+  if (rc || !grew) return rc;
   hipStream_t aux;
-  if (int rc = aux_stream(c, &aux)) return rc;
+  if ((rc = aux_stream(c, &aux))) return rc;
   hipError_t e = hipMemsetAsync(c->d_pk, 0, 2 * sizeof(h2s::PeakState), aux);
   if (e == hipSuccess) e = hipStreamSynchronize(aux);
   return e == hipSuccess ? 0 : hip_fail(c, e, "peak state reset");
 }
 
-// the statistics, the curves and the state are one context's scratch: a call
-// on another stream waits (on the device) for the previous call's use of
-// them, so consecutive calls see the state in call order
-static int peak_order(h2s_ctx* c, hipStream_t s) {
-  if (!c->peak_ev) {
-    hipError_t e = hipEventCreateWithFlags(&c->peak_ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      c->peak_ev = nullptr;
-      return hip_fail(c, e, "peak event");
-    }
-  }
-  if (!c->peak_pending) return 0;
-  hipError_t e = hipStreamWaitEvent(s, c->peak_ev, 0);
-  return e == hipSuccess ? 0 : hip_fail(c, e, "peak ordering");
-}
+// the statistics, the curves and the state are one context's scratch
+// (c->peak_use): a call on another stream waits (on the device) for the
+// previous call's use of them, so consecutive calls see the state in call order
+static int peak_order(h2s_ctx* c, hipStream_t s) { return c->peak_use.wait(c, s, "peak ordering"); }
 
-static int peak_done(h2s_ctx* c, hipStream_t s) {
-  hipError_t e = hipEventRecord(c->peak_ev, s);
-  if (e != hipSuccess) return hip_fail(c, e, "peak event");
-  c->peak_pending = true;
-  return 0;
-}
+static int peak_done(h2s_ctx* c, hipStream_t s) { return c->peak_use.mark(c, s, "peak event"); }
 
 // per-frame statistic (PQ peak measurement, average PQ) of the batch k binds
 // into c->d_fstat, queued on s as two launches (k_peak_stats*, then
@@ -1303,22 +1319,15 @@ static int frame_stats(h2s_ctx* c, const KParams& k, int nframes, hipStream_t s,
   if (nframes > c->stats_nf) {
     const size_t nf = (size_t)nframes;
     const size_t part = nf * h2s::PEAK_BLOCKS_MAX * sizeof(float2), zero = (nf * h2s::PEAK_BINS + 1) * sizeof(unsigned);
-    if (c->d_stats) hipFree(c->d_stats);
-    c->d_stats = nullptr;
     c->stats_nf = 0;
-    if (hipMalloc(&c->d_stats, part + zero) != hipSuccess) {
-      c->d_stats = nullptr;
-      return fail(c, H2S_E_OOM, "peak statistics allocation failed");
-    }
-    hipError_t e = hipMemsetAsync(static_cast<char*>(c->d_stats) + part, 0, zero, s);
+    if (int rc = c->d_stats.reserve(c, part + zero, "peak statistics")) return rc;
+    hipError_t e = hipMemsetAsync(c->d_stats + nf * h2s::PEAK_BLOCKS_MAX, 0, zero, s);
     if (e != hipSuccess) return hip_fail(c, e, "peak statistics clear");
     c->stats_nf = nframes;
   }
-  if (int rc = ensure_dev(c, (void**)&c->d_fstat, &c->fstat_cap, (size_t)(f0 + nframes) * sizeof(double2),
-                         "peak statistics"))
-    return rc;
+  if (int rc = c->d_fstat.reserve(c, (size_t)(f0 + nframes) * sizeof(double2), "peak statistics")) return rc;
   const size_t nf = (size_t)c->stats_nf;
-  float2* d_part = static_cast<float2*>(c->d_stats);
+  float2* d_part = c->d_stats;
   h2s::PeakTail T;
   T.M = m;
   T.fstat = c->d_fstat + f0;
@@ -1345,20 +1354,11 @@ static KParams frame_range(const KParams& k, int f0, int n) {
 }
 
 static int peak_streams(h2s_ctx* c, int nev) {
-  for (hipStream_t& ps : c->pk_s)
-    if (!ps) {
-      hipError_t e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-      if (e != hipSuccess) {
-        ps = nullptr;
-        return hip_fail(c, e, "peak stream");
-      }
-    }
-  while ((int)c->pk_ev.size() < nev) {
-    hipEvent_t ev;
-    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) return hip_fail(c, e, "peak event");
-    c->pk_ev.push_back(ev);
-  }
+  for (Stream& ps : c->pk_s)
+    if (int rc = ps.get(c, "peak stream")) return rc;
+  if ((int)c->pk_ev.size() < nev) c->pk_ev.resize(nev);
+  for (Event& ev : c->pk_ev)
+    if (int rc = ev.get(c, "peak event")) return rc;
   return 0;
 }
 
@@ -1372,11 +1372,10 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
   int rc;
   // every allocation before the first launch (hipFree of a grown buffer
   // would wait for the device)
-  if ((rc = peak_streams(c, nch + 2)) ||
-      (rc = ensure_dev(c, (void**)&c->d_fstat, &c->fstat_cap, (size_t)nframes * sizeof(double2), "peak statistics")))
+  if ((rc = peak_streams(c, nch + 2)) || (rc = c->d_fstat.reserve(c, (size_t)nframes * sizeof(double2), "peak statistics")))
     return rc;
-  hipStream_t ss = c->pk_s[0], st[2] = {s, c->pk_s[1]};
-  hipEvent_t ev_start = c->pk_ev[0], ev_end = c->pk_ev[1];
+  hipStream_t ss = c->pk_s[0].s, st[2] = {s, c->pk_s[1].s};
+  hipEvent_t ev_start = c->pk_ev[0].ev, ev_end = c->pk_ev[1].ev;
   hipError_t e = hipEventRecord(ev_start, s);
   if (e == hipSuccess) e = hipStreamWaitEvent(ss, ev_start, 0);
   if (e == hipSuccess) e = hipStreamWaitEvent(st[1], ev_start, 0);
@@ -1393,7 +1392,7 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
     const int f0 = j * C, n = std::min(C, nframes - f0);
     const KParams kj = frame_range(k, f0, n);
     if ((rc = frame_stats(c, kj, n, ss, c->d_pk, c->d_curve + f0, f0))) return fail_joined(rc);
-    hipEvent_t ev = c->pk_ev[2 + j];
+    hipEvent_t ev = c->pk_ev[2 + j].ev;
     if ((e = hipEventRecord(ev, ss)) != hipSuccess || (e = hipStreamWaitEvent(st[j & 1], ev, 0)) != hipSuccess)
       return fail_joined(hip_fail(c, e, "peak schedule"));
     if ((e = launch_chain(c, kj, true, vec, out8, n, st[j & 1], c->d_curve + f0, false)) != hipSuccess)
@@ -1401,7 +1400,7 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
   }
   // s joins the statistics stream (the state) and the second conversion stream
   if ((e = hipEventRecord(ev_end, st[1])) != hipSuccess || (e = hipStreamWaitEvent(s, ev_end, 0)) != hipSuccess ||
-      (e = hipStreamWaitEvent(s, c->pk_ev[2 + nch - 1], 0)) != hipSuccess)
+      (e = hipStreamWaitEvent(s, c->pk_ev[2 + nch - 1].ev, 0)) != hipSuccess)
     return fail_joined(hip_fail(c, e, "peak schedule"));
   return peak_done(c, s);
 }
@@ -1414,8 +1413,7 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
 static int run_dynamic_peak(h2s_ctx* c, const KParams& k, bool fast, bool vec, bool out8, int nframes, hipStream_t s) {
   int rc;
   if ((rc = ensure_peak_state(c)) || (rc = peak_order(c, s))) return rc;
-  if ((rc = ensure_dev(c, (void**)&c->d_curve, &c->curve_cap, (size_t)nframes * sizeof(h2s::CurveConsts), "curve records")))
-    return rc;
+  if ((rc = c->d_curve.reserve(c, (size_t)nframes * sizeof(h2s::CurveConsts), "curve records"))) return rc;
   if (fast && (k.W & (h2s::TBW - 1)) == 0 && c->peak_chunk > 0 && nframes > c->peak_chunk)
     return run_dynamic_peak_chunked(c, k, vec, out8, nframes, s);
   if ((rc = frame_stats(c, k, nframes, s, c->d_pk, c->d_curve))) return rc;
@@ -1441,12 +1439,7 @@ static int run_dynamic_peak(h2s_ctx* c, const KParams& k, bool fast, bool vec, b
 static int peak_sync(h2s_ctx* c, hipStream_t* aux) {
   int rc;
   if ((rc = drain_launches(c)) || (rc = ensure_peak_state(c)) || (rc = aux_stream(c, aux))) return rc;
-  if (c->peak_pending) {
-    hipError_t e = hipEventSynchronize(c->peak_ev);
-    if (e != hipSuccess) return hip_fail(c, e, "peak launches");
-    c->peak_pending = false;
-  }
-  return 0;
+  return c->peak_use.sync_host(c, "peak launches");
 }
 
 int h2s_peak_reset(h2s_ctx* c) {
@@ -1469,7 +1462,7 @@ int h2s_peak_feed(h2s_ctx* c, const double* fmax, const double* favg, int n) {
   DeviceGuard g(c->device);
   hipStream_t aux;
   if ((rc = peak_sync(c, &aux))) return rc;
-  if ((rc = ensure_dev(c, (void**)&c->d_fstat, &c->fstat_cap, (size_t)n * sizeof(double2), "peak statistics"))) return rc;
+  if ((rc = c->d_fstat.reserve(c, (size_t)n * sizeof(double2), "peak statistics"))) return rc;
   std::vector<double2> st(n);
   for (int i = 0; i < n; i++) st[i] = make_double2(fmax[i], favg[i]);
   // the same device IIR as h2s_process (bit-identical state either way)
@@ -1526,6 +1519,22 @@ static h2s_frames frames_at(const h2s_frames* f, int start) {
   return t;
 }
 
+// kernel timing (h2s_set_timing): one pair of the event ring around a call's
+// launches on s, read back by h2s_kernel_ms
+static void timing_begin(h2s_ctx* c, hipStream_t s) {
+  if (!c->timing) return;
+  Event &e0 = c->ev0[c->ev_count % kEvRing], &e1 = c->ev1[c->ev_count % kEvRing];
+  (void)e0.get(c, "timing event", hipEventDefault);
+  (void)e1.get(c, "timing event", hipEventDefault);
+  hipEventRecord(e0.ev, s);
+}
+
+static void timing_end(h2s_ctx* c, hipStream_t s) {
+  if (!c->timing) return;
+  hipEventRecord(c->ev1[c->ev_count % kEvRing].ev, s);
+  c->ev_count++;
+}
+
 // Host frames in and/or out: the batch is cut into up to kMaxChunks chunks of
 // whole frames; chunk i's H2D copy, kernel and D2H copy run on three streams
 // so that copies of neighbouring chunks overlap the kernel and each other.
@@ -1537,30 +1546,20 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
                              const h2s_frames& din, const h2s_frames& dout, int nframes, bool fast, bool vec,
                              bool out8, hipStream_t s, bool dyn_peak) {
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
-  for (hipStream_t& ps : c->ps)
-    if (!ps) {
-      hipError_t e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-      if (e != hipSuccess) {
-        ps = nullptr;
-        return hip_fail(c, e, "pipeline stream");
-      }
-    }
-  for (hipEvent_t& ev : c->pev)
-    if (!ev) {
-      hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (e != hipSuccess) {
-        ev = nullptr;
-        return hip_fail(c, e, "pipeline event");
-      }
-    }
-  hipStream_t s_in = c->ps[0], s_cmp = c->ps[1], s_out = c->ps[2];
+  for (Stream& ps : c->ps)
+    if (int rc = ps.get(c, "pipeline stream")) return rc;
+  for (Event& ev : c->pev)
+    if (int rc = ev.get(c, "pipeline event")) return rc;
+  hipStream_t s_in = c->ps[0].s, s_cmp = c->ps[1].s, s_out = c->ps[2].s;
+  auto sync_all = [&] {
+    for (Stream& ps : c->ps) hipStreamSynchronize(ps.s);
+  };
   const int per = (nframes + kMaxChunks - 1) / kMaxChunks, nch = (nframes + per - 1) / per;
-  hipEvent_t ev_start = c->pev[2 * kMaxChunks], ev_done = c->pev[2 * kMaxChunks + 1];
+  hipEvent_t ev_start = c->pev[2 * kMaxChunks].ev, ev_done = c->pev[2 * kMaxChunks + 1].ev;
   hipError_t e = hipEventRecord(ev_start, s);
-  for (hipStream_t ps : c->ps)
-    if (e == hipSuccess) e = hipStreamWaitEvent(ps, ev_start, 0);
+  for (Stream& ps : c->ps)
+    if (e == hipSuccess) e = hipStreamWaitEvent(ps.s, ev_start, 0);
   if (e != hipSuccess) return hip_fail(c, e, "pipeline ordering");
-  const int slot = (int)(c->ev_count % kEvRing);
   const char* what = nullptr;
   for (int i = 0; i < nch && !what; i++) {
     const int f0 = i * per, nf = nframes - f0 < per ? nframes - f0 : per;
@@ -1568,21 +1567,15 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     if (host_in) {
       const h2s_frames hi = frames_at(in, f0);
       if ((e = copy_frames(&ci, &hi, nf, s_in)) != hipSuccess) what = "host->device copy";
-      else if ((e = hipEventRecord(c->pev[i], s_in)) != hipSuccess) what = "pipeline event";
-      else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i], 0)) != hipSuccess) what = "pipeline ordering";
+      else if ((e = hipEventRecord(c->pev[i].ev, s_in)) != hipSuccess) what = "pipeline event";
+      else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       if (what) break;
     }
-    if (c->timing && i == 0) {
-      if (!c->ev0[slot]) {
-        hipEventCreate(&c->ev0[slot]);
-        hipEventCreate(&c->ev1[slot]);
-      }
-      hipEventRecord(c->ev0[slot], s_cmp);
-    }
+    if (i == 0) timing_begin(c, s_cmp);
     fill_geometry(&k, &ci, &co, nf);
     if (dyn_peak) {
       if (int rc = run_dynamic_peak(c, k, fast, vec, out8, nf, s_cmp)) {
-        for (hipStream_t ps : c->ps) hipStreamSynchronize(ps);
+        sync_all();
         return rc;
       }
     } else if ((e = launch_chain(c, k, fast, vec, out8, nf, s_cmp)) != hipSuccess) {
@@ -1590,24 +1583,21 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     }
     if (!what && host_out) {
       const h2s_frames ho = frames_at(out, f0);
-      if ((e = hipEventRecord(c->pev[kMaxChunks + i], s_cmp)) != hipSuccess) what = "pipeline event";
-      else if ((e = hipStreamWaitEvent(s_out, c->pev[kMaxChunks + i], 0)) != hipSuccess) what = "pipeline ordering";
+      if ((e = hipEventRecord(c->pev[kMaxChunks + i].ev, s_cmp)) != hipSuccess) what = "pipeline event";
+      else if ((e = hipStreamWaitEvent(s_out, c->pev[kMaxChunks + i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       else if ((e = copy_frames(&ho, &co, nf, s_out)) != hipSuccess) what = "device->host copy";
     }
   }
   if (what) {  // drain whatever was queued before returning the caller's buffers
-    for (hipStream_t ps : c->ps) hipStreamSynchronize(ps);
+    sync_all();
     return hip_fail(c, e, what);
   }
-  if (c->timing) {
-    hipEventRecord(c->ev1[slot], s_cmp);
-    c->ev_count++;
-  }
+  timing_end(c, s_cmp);
   // s waits for the last stream of the chain (D2H if any, else compute)
   if ((e = hipEventRecord(ev_done, host_out ? s_out : s_cmp)) == hipSuccess) e = hipStreamWaitEvent(s, ev_done, 0);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
-    for (hipStream_t ps : c->ps) hipStreamSynchronize(ps);
+    sync_all();
     return hip_fail(c, e, "stream synchronize");
   }
   return 0;
@@ -1633,19 +1623,9 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   if (host_in || host_out) {
     const size_t ib = host_in ? frame_bytes(in) * nframes : 0, ob = host_out ? frame_bytes(out) * nframes : 0;
     const size_t need = ((ib + 255) / 256) * 256 + ob;
-    if (need > c->stage_bytes) {
-      if (c->d_stage) hipFree(c->d_stage);
-      c->d_stage = nullptr;
-      c->stage_bytes = 0;
-      hipError_t e = hipMalloc(&c->d_stage, need);
-      if (e != hipSuccess) {
-        c->d_stage = nullptr;
-        return fail(c, H2S_E_OOM, "staging allocation failed");
-      }
-      c->stage_bytes = need;
-    }
+    if ((rc = c->d_stage.reserve(c, need, "staging"))) return rc;
     if (host_in) din = tight(in, c->d_stage);
-    if (host_out) dout = tight(out, (uint8_t*)c->d_stage + ((ib + 255) / 256) * 256);
+    if (host_out) dout = tight(out, c->d_stage + ((ib + 255) / 256) * 256);
   }
   fill_geometry(&k, &din, &dout, nframes);
   const bool vec = vec_ok(&din, false) && vec_ok(&dout, out8);
@@ -1660,17 +1640,7 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
     if ((rc = ensure_chr(c, k))) return rc;
     // one context scratch (d_chr) for every two-pass launch: a launch on
     // another stream waits until the previous one has finished with it
-    if (!c->chr_ev) {
-      hipError_t e = hipEventCreateWithFlags(&c->chr_ev, hipEventDisableTiming);
-      if (e != hipSuccess) {
-        c->chr_ev = nullptr;
-        return hip_fail(c, e, "two-pass event");
-      }
-    }
-    if (c->chr_pending) {
-      hipError_t e = hipStreamWaitEvent(s, c->chr_ev, 0);
-      if (e != hipSuccess) return hip_fail(c, e, "two-pass ordering");
-    }
+    if ((rc = c->chr_use.wait(c, s, "two-pass ordering"))) return rc;
   }
   const bool dyn_peak = c->params.peak_detect &&
                         (k.tonemap == H2S_TM_BT2390 || k.tonemap == H2S_TM_SPLINE || k.pipe == h2s::PIPE_LIBPLACEBO);
@@ -1683,14 +1653,7 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
     hipError_t e = copy_frames(&din, in, nframes, s);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "host->device copy"));
   }
-  const int slot = (int)(c->ev_count % kEvRing);
-  if (c->timing) {
-    if (!c->ev0[slot]) {
-      hipEventCreate(&c->ev0[slot]);
-      hipEventCreate(&c->ev1[slot]);
-    }
-    hipEventRecord(c->ev0[slot], s);
-  }
+  timing_begin(c, s);
   hipError_t e;
   if (dyn_peak) {
     if ((rc = run_dynamic_peak(c, k, fast, vec, out8, nframes, s))) return queued_exit(c, s, rc);
@@ -1703,18 +1666,12 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
     return queued_exit(c, s, fail(c, H2S_E_HIP, "injected failure after the launch (H2S_OPT_TEST_FAIL_AFTER_LAUNCH)"));
   }
   if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "kernel launch"));
-  if (c->timing) {
-    hipEventRecord(c->ev1[slot], s);
-    c->ev_count++;
-  }
+  timing_end(c, s);
   if (host_out) {
     e = copy_frames(out, &dout, nframes, s);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "device->host copy"));
   }
-  if (two_pass) {
-    if ((e = hipEventRecord(c->chr_ev, s)) != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "two-pass event"));
-    c->chr_pending = true;
-  }
+  if (two_pass && (rc = c->chr_use.mark(c, s, "two-pass event"))) return queued_exit(c, s, rc);
   if (host_in || host_out) {
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "stream synchronize"));
@@ -1741,17 +1698,14 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   fo.width = in->width, fo.height = in->height, fo.bits = c->params.bits_out, fo.location = H2S_LOC_DEVICE;
   const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in) + 255) / 256 * 256 : 0;
   const size_t fb = (frame_bytes(&fo) + 255) / 256 * 256, pb = out_location == H2S_LOC_HOST ? ob : 0;
-  void* scratch = nullptr;
-  hipError_t e = hipMalloc(&scratch, ib + fb + pb + 256);
-  if (e != hipSuccess) return fail(c, H2S_E_OOM, "debug alloc");
-  uint8_t* base = (uint8_t*)scratch;
+  Dev<uint8_t> scratch;  // freed on every exit, after s has been waited for
+  if ((rc = scratch.reserve(c, ib + fb + pb + 256, "debug"))) return rc;
+  uint8_t* base = scratch;
   h2s_frames din = *in;
+  hipError_t e;
   if (in->location == H2S_LOC_HOST) {
     din = tight(in, base);
-    if ((e = copy_frames(&din, in, 1, s)) != hipSuccess) {
-      hipFree(scratch);
-      return hip_fail(c, e, "debug copy");
-    }
+    if ((e = copy_frames(&din, in, 1, s)) != hipSuccess) return hip_fail(c, e, "debug copy");
   }
   fo = tight(&fo, base + ib);
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
@@ -1764,7 +1718,6 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   if (e == hipSuccess && (path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL)) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
-      hipFree(scratch);
       return rc;
     }
     e = launch_chain(c, k, true, false, out8, 1, s, nullptr, false, stage, dout);
@@ -1772,7 +1725,6 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   if (e == hipSuccess && out_location == H2S_LOC_HOST) e = hipMemcpyAsync(out_rgb, dout, ob, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   hipStreamSynchronize(s);
-  hipFree(scratch);
   if (e != hipSuccess) return hip_fail(c, e, "debug kernel");
   return 0;
 }
@@ -1936,22 +1888,13 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
                              : 0;
   const size_t rgb_b = rgb_location == H2S_LOC_HOST ? al((size_t)out_w * 3 * out_h * n) : 0;
   const size_t need = yuv_b + syuv_b + tab_b + rgb_b + 256;
-  if (need > c->prev_bytes) {
-    if (c->d_prev) {
-      // a previous preview's kernels may still read the old scratch
-      drain_launches(c);
-      hipStreamSynchronize(s);
-      hipFree(c->d_prev);
-    }
-    c->d_prev = nullptr;
-    c->prev_bytes = 0;
-    if (hipMalloc(&c->d_prev, need) != hipSuccess) {
-      c->d_prev = nullptr;
-      return fail(c, H2S_E_OOM, "preview scratch allocation failed");
-    }
-    c->prev_bytes = need;
+  if (need > c->d_prev.cap && c->d_prev) {
+    // a previous preview's kernels may still read the old scratch
+    drain_launches(c);
+    hipStreamSynchronize(s);
   }
-  uint8_t* base = (uint8_t*)c->d_prev;
+  if ((rc = c->d_prev.reserve(c, need, "preview scratch"))) return rc;
+  uint8_t* base = c->d_prev;
   h2s_frames y8{};
   y8.width = W, y8.height = H, y8.bits = 8, y8.location = H2S_LOC_DEVICE;
   y8 = tight(&y8, base);
@@ -2068,9 +2011,9 @@ double h2s_kernel_ms(h2s_ctx* c, int count) {
   double sum = 0.0;
   for (int i = 0; i < count; i++) {
     const int slot = (int)((c->ev_count - 1 - i) % kEvRing);
-    if (hipEventSynchronize(c->ev1[slot]) != hipSuccess) return -1.0;
+    if (hipEventSynchronize(c->ev1[slot].ev) != hipSuccess) return -1.0;
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev0[slot], c->ev1[slot]) != hipSuccess) return -1.0;
+    if (hipEventElapsedTime(&ms, c->ev0[slot].ev, c->ev1[slot].ev) != hipSuccess) return -1.0;
     sum += ms;
   }
   return sum / count;

@@ -23,7 +23,10 @@
  * the context has queued (on any stream) to finish, so replacing the tables a
  * kernel in flight reads is safe; they wait on events recorded after the
  * context's own launches only, never on other contexts or on unrelated work
- * on the device.
+ * on the device.  One context may be given different streams from call to
+ * call: scratch that its calls share (the BICUBIC plane, the peak state, and
+ * the tables the first h2s_process after h2s_set_lut derives from the lattice
+ * on its own stream) is ordered across those streams on the device.
  *
  * Errors: 0 on success, a negative H2S_E_* code otherwise; the message is
  * available from h2s_last_error(ctx) (or h2s_last_error(NULL) for failures

@@ -678,6 +678,44 @@ def test_two_pass_scratch_serialised_across_streams(tm):
     assert np.array_equal(d2.to_numpy().buf, want2)
 
 
+@pytest.mark.parametrize('case', ['libplacebo', 'cpu_chain'])
+def test_derived_lattice_build_ordered_across_streams(tm, case):
+    """The tile kernel's derived lattice (the libplacebo branch's 2^24-entry
+    lut3d table, the CPU chain's pre-multiplied d_lut_yuv) is rebuilt on the
+    stream of the first call after h2s_set_lut; a call that follows at once
+    on another stream waits for that build, so both outputs equal the serial
+    result.  Guards the ADVICE r06 finding (the build had no cross-stream
+    ordering); the ordering itself is argued from the code, a race cannot be
+    made to fail reliably."""
+    import torch
+    from hdr2sdr import _abi
+    W, H, n = 64, 32, 2                       # one whole tile: the smallest frame, the widest window
+    params, lut_n = {'libplacebo': (hdr2sdr.TonemapParams(tonemapper='bt.2390', pipeline='libplacebo'), 33),
+                     'cpu_chain': (hdr2sdr.TonemapParams(tonemapper='hable', gamma=2.2), 65)}[case]
+    tm.set_params(params)
+    tm.set_lut(lattice(lut_n))
+    c1 = synth_frames('smooth', n, W, H, 10, device='cpu', seed=71)
+    c2 = synth_frames('uniform', n, W, H, 10, device='cpu', seed=72)
+    s1, s2 = c1.to_torch('cuda'), c2.to_torch('cuda')
+    d1 = hdr2sdr.FrameBatch.empty_torch(n, W, H, 10, 'cuda')
+    d2 = hdr2sdr.FrameBatch.empty_torch(n, W, H, 10, 'cuda')
+    assert tm.query_path(s1, d1) == _abi.PATH_TILE
+    want1, want2 = tm(s1).to_numpy().buf, tm(s2).to_numpy().buf
+    op = oracle.params_from(params.to_c())
+    for want, cpu in ((want1, c1), (want2, c2)):
+        src = cpu.to_numpy().buf
+        ref = oracle.process(op, lattice(lut_n), src, W, H).astype(np.int64)
+        assert_close_int(params, want.astype(np.int64), ref, W, H, src, lut_n=lut_n)
+    tm.set_lut(lattice(lut_n))                # the same lattice: invalidates the derived table
+    torch.cuda.synchronize()
+    stA, stB = torch.cuda.Stream(), torch.cuda.Stream()
+    tm.process(s1, d1, stA)
+    tm.process(s2, d2, stB)
+    torch.cuda.synchronize()
+    assert np.array_equal(d1.to_numpy().buf, want1)
+    assert np.array_equal(d2.to_numpy().buf, want2)
+
+
 def test_peak_exchange_and_lp_tone_errors(tm):
     """h2s_peak_stats takes device frames only; h2s_peak_feed rejects
     mismatched arrays; an unknown lp_tone is INVALID_ARG at set_params (the
