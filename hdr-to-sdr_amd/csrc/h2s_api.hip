@@ -178,6 +178,8 @@ struct __attribute__((visibility("hidden"))) h2s_ctx {
   Ordered lut_built;      // after the last build of d_lut_yuv / d_lut8x (queued on the caller's stream)
   bool fast_enabled = true;
   bool lp_exact = false;  // H2S_OPT_LP_EXACT
+  // h2s_set_frame_layout: how later calls read `in` and write `out` (enum h2s_layout)
+  int in_layout = H2S_LAYOUT_PLANAR, out_layout = H2S_LAYOUT_PLANAR;
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
@@ -601,7 +603,9 @@ void build_hlg_table(std::vector<float4>* out) {
 
 bool aligned(const void* p, long long a) { return ((uintptr_t)p % (uintptr_t)a) == 0; }
 
-int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which) {
+// semi (here and below): the set is semi-planar (H2S_LAYOUT_SEMI): plane 1
+// holds (Cb, Cr) pairs, a row of it is as long as a luma row, plane 2 is unused
+int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi = 0) {
   if (!f) return fail(c, H2S_E_INVALID_ARG, std::string(which) + " frames is NULL");
   if (f->width <= 0 || f->height <= 0) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": empty frame");
   if ((f->width & 1) || (f->height & 1))
@@ -612,34 +616,43 @@ int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which) {
   if (f->location != H2S_LOC_DEVICE && f->location != H2S_LOC_HOST)
     return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": bad location");
   const int bps = bits == 8 ? 1 : 2;
-  const long long rowb[3] = {(long long)f->width * bps, (long long)f->width / 2 * bps, (long long)f->width / 2 * bps};
-  for (int p = 0; p < 3; p++) {
+  const long long crow = (long long)f->width / 2 * bps * (semi ? 2 : 1);
+  const long long rowb[3] = {(long long)f->width * bps, crow, crow};
+  for (int p = 0; p < (semi ? 2 : 3); p++) {
     if (!f->data[p]) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": NULL plane");
     if (f->linesize[p] < rowb[p])
       return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": linesize smaller than a row");
     if (bps == 2 && ((f->linesize[p] & 1) || !aligned(f->data[p], 2)))
       return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": 16-bit planes must be 2-byte aligned");
+    if (semi && bps == 2 && (f->frame_pitch[p] & 1))
+      return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": 16-bit planes need an even frame pitch");
   }
   return 0;
 }
 
 // vector path needs 16-B luma / 8-B chroma alignment of every row start
-bool vec_ok(const h2s_frames* f, bool out8) {
-  const long long ay = out8 ? 8 : 16, ac = out8 ? 4 : 8;
+// (semi-planar: four pairs of the interleaved plane are one luma-sized access)
+bool vec_ok(const h2s_frames* f, bool out8, int semi = 0) {
+  const long long ay = out8 ? 8 : 16, ac = semi ? ay : (out8 ? 4 : 8);
   const long long a[3] = {ay, ac, ac};
-  for (int p = 0; p < 3; p++)
+  for (int p = 0; p < (semi ? 2 : 3); p++)
     if (!aligned(f->data[p], a[p]) || f->linesize[p] % a[p] || f->frame_pitch[p] % a[p]) return false;
   return true;
 }
 
 // tile kernel: at least one 64-pixel tile, every row start 16-B aligned (8-B
 // for 8-bit chroma output)
-bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw) {
+// (semi-planar: the same for the two planes it has)
+bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, int in_semi = 0, int out_semi = 0) {
   if (in->width < tw) return false;  // width % tw columns go to k_process (launch_chain)
   for (int p = 0; p < 3; p++) {
-    if (!aligned(in->data[p], 16) || in->linesize[p] % 16 || in->frame_pitch[p] % 16) return false;
+    if (!(in_semi && p == 2) &&
+        (!aligned(in->data[p], 16) || in->linesize[p] % 16 || in->frame_pitch[p] % 16))
+      return false;
     const long long a = out8 ? (p ? 8 : 8) : 16;
-    if (!aligned(out->data[p], a) || out->linesize[p] % a || out->frame_pitch[p] % a) return false;
+    if (!(out_semi && p == 2) &&
+        (!aligned(out->data[p], a) || out->linesize[p] % a || out->frame_pitch[p] % a))
+      return false;
   }
   return true;
 }
@@ -650,7 +663,9 @@ size_t frame_bytes(const h2s_frames* f) {
 }
 
 // tight device copy descriptor laid out in `base`
-h2s_frames tight(const h2s_frames* f, void* base) {
+// (semi-planar: the interleaved plane takes the two chroma planes' place,
+// so a frame's bytes are the same)
+h2s_frames tight(const h2s_frames* f, void* base, int semi = 0) {
   h2s_frames t = *f;
   const long long bps = f->bits == 8 ? 1 : 2;
   const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4;
@@ -661,27 +676,31 @@ h2s_frames tight(const h2s_frames* f, void* base) {
   t.linesize[0] = f->width * bps;
   t.linesize[1] = t.linesize[2] = f->width / 2 * bps;
   t.frame_pitch[0] = t.frame_pitch[1] = t.frame_pitch[2] = fb;
+  if (semi) t.data[2] = nullptr, t.linesize[1] = f->width * bps, t.linesize[2] = 0, t.frame_pitch[2] = 0;
   t.location = H2S_LOC_DEVICE;
   return t;
 }
 
 // the whole batch is one contiguous span laid out as tight() describes
-bool is_tight(const h2s_frames* f) {
+bool is_tight(const h2s_frames* f, int semi = 0) {
   const long long bps = f->bits == 8 ? 1 : 2;
   const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4, fb = ysz + 2 * csz;
+  if (semi)
+    return f->linesize[0] == f->width * bps && f->linesize[1] == f->width * bps && f->frame_pitch[0] == fb &&
+           f->frame_pitch[1] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz;
   return f->linesize[0] == f->width * bps && f->linesize[1] == f->width / 2 * bps &&
          f->linesize[2] == f->width / 2 * bps && f->frame_pitch[0] == fb && f->frame_pitch[1] == fb &&
          f->frame_pitch[2] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz &&
          (const uint8_t*)f->data[2] == (const uint8_t*)f->data[1] + csz;
 }
 
-hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s) {
+hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi = 0) {
   const long long bps = src->bits == 8 ? 1 : 2;
-  if (is_tight(src) && is_tight(dst))  // one DMA for the whole batch
+  if (is_tight(src, semi) && is_tight(dst, semi))  // one DMA for the whole batch
     return hipMemcpyAsync(dst->data[0], src->data[0], (size_t)src->frame_pitch[0] * nframes, hipMemcpyDefault, s);
   for (int fr = 0; fr < nframes; fr++)
-    for (int p = 0; p < 3; p++) {
-      const long long w = (p ? src->width / 2 : src->width) * bps, h = p ? src->height / 2 : src->height;
+    for (int p = 0; p < (semi ? 2 : 3); p++) {
+      const long long w = (p && !semi ? src->width / 2 : src->width) * bps, h = p ? src->height / 2 : src->height;
       hipError_t e = hipMemcpy2DAsync((uint8_t*)dst->data[p] + fr * dst->frame_pitch[p], dst->linesize[p],
                                       (const uint8_t*)src->data[p] + fr * src->frame_pitch[p], src->linesize[p], w,
                                       h, hipMemcpyDefault, s);
@@ -690,7 +709,12 @@ hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes
   return hipSuccess;
 }
 
-void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes) {
+// in_semi / out_semi: the sets' layouts (h2s_set_frame_layout).  A semi-planar
+// set is bound with plane 2 as plane 1 one sample on, samples two apart, so
+// the kernels address both layouts alike; 16-bit words carry the code in
+// their high bits
+void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes, int in_semi,
+                   int out_semi) {
   k->W = in->width;
   k->H = in->height;
   k->cw = in->width / 2;
@@ -707,6 +731,17 @@ void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int 
       k->out_ls[p] = out->linesize[p];
       k->out_fp[p] = out->frame_pitch[p];
     }
+  }
+  k->in_cstep = k->out_cstep = 1, k->in_sh = k->out_sh = 0;
+  if (in_semi) {
+    k->in[2] = k->in[1] + 2, k->in_ls[2] = k->in_ls[1], k->in_fp[2] = k->in_fp[1];
+    k->in_cstep = 2, k->in_sh = 16 - in->bits;
+    k->in_mask &= 0xFFFFu >> k->in_sh;
+  }
+  if (out && out_semi) {
+    const int bps = out->bits == 8 ? 1 : 2;
+    k->out[2] = k->out[1] + bps, k->out_ls[2] = k->out_ls[1], k->out_fp[2] = k->out_fp[1];
+    k->out_cstep = 2, k->out_sh = bps == 2 ? 16 - out->bits : 0;
   }
 }
 
@@ -1207,6 +1242,7 @@ static hipError_t launch_chain(const h2s_ctx* c, const KParams& k, bool fast, bo
   const int w64 = k.W & ~(tw - 1);
   F.W = w64, F.H = k.H, F.cw = k.cw, F.ch = k.ch;
   F.chroma_edge = k.chroma_edge;
+  F.in_semi = k.in_cstep == 2, F.in_sh = k.in_sh, F.out_semi = k.out_cstep == 2, F.out_sh = k.out_sh;
   for (int p = 0; p < 3; p++) {
     const long long ib = (long long)(p ? k.ch : k.H) * k.in_ls[p], ob = (long long)(p ? k.ch : k.H) * k.out_ls[p];
     F.in_bytes[p] = (int)(ib < 0x7fffffff ? ib : 0x7fffffff);
@@ -1255,7 +1291,7 @@ static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
 static int choose_path(const h2s_ctx* c, const KParams& k, const h2s_frames* din, const h2s_frames* dout,
                        bool out8) {
   const int tw = h2s::TBW;
-  if (fast_params_ok(c, k) && tile_ok(din, dout, out8, tw))
+  if (fast_params_ok(c, k) && tile_ok(din, dout, out8, tw, k.in_cstep == 2, k.out_cstep == 2))
     return (din->width & (tw - 1)) ? H2S_PATH_TILE_TAIL : H2S_PATH_TILE;
   return c->params.chroma_filter == H2S_CHROMA_BICUBIC ? H2S_PATH_TWO_PASS : H2S_PATH_GENERIC;
 }
@@ -1496,13 +1532,13 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   KParams k;
   int rc = prepare(c, &k, false);  // the statistics need no LUT
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input"))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
   if (in->location != H2S_LOC_DEVICE) return fail(c, H2S_E_INVALID_ARG, "h2s_peak_stats takes device frames");
   if (nframes == 0) return 0;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   h2s_frames out = *in;                       // geometry only: the statistics read the input planes
-  fill_geometry(&k, in, &out, nframes);
+  fill_geometry(&k, in, &out, nframes, c->in_layout, 0);
   if ((rc = peak_order(c, s)) || (rc = frame_stats(c, k, nframes, s, nullptr, nullptr))) return rc;
   std::vector<double2> st(nframes);
   hipError_t e = hipMemcpyAsync(st.data(), c->d_fstat, nframes * sizeof(double2), hipMemcpyDeviceToHost, s);
@@ -1566,13 +1602,13 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     const h2s_frames ci = frames_at(&din, f0), co = frames_at(&dout, f0);
     if (host_in) {
       const h2s_frames hi = frames_at(in, f0);
-      if ((e = copy_frames(&ci, &hi, nf, s_in)) != hipSuccess) what = "host->device copy";
+      if ((e = copy_frames(&ci, &hi, nf, s_in, c->in_layout)) != hipSuccess) what = "host->device copy";
       else if ((e = hipEventRecord(c->pev[i].ev, s_in)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       if (what) break;
     }
     if (i == 0) timing_begin(c, s_cmp);
-    fill_geometry(&k, &ci, &co, nf);
+    fill_geometry(&k, &ci, &co, nf, c->in_layout, c->out_layout);
     if (dyn_peak) {
       if (int rc = run_dynamic_peak(c, k, fast, vec, out8, nf, s_cmp)) {
         sync_all();
@@ -1585,7 +1621,7 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
       const h2s_frames ho = frames_at(out, f0);
       if ((e = hipEventRecord(c->pev[kMaxChunks + i].ev, s_cmp)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_out, c->pev[kMaxChunks + i].ev, 0)) != hipSuccess) what = "pipeline ordering";
-      else if ((e = copy_frames(&ho, &co, nf, s_out)) != hipSuccess) what = "device->host copy";
+      else if ((e = copy_frames(&ho, &co, nf, s_out, c->out_layout)) != hipSuccess) what = "device->host copy";
     }
   }
   if (what) {  // drain whatever was queued before returning the caller's buffers
@@ -1609,8 +1645,9 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input"))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output"))) return rc;
+  const int in_semi = c->in_layout, out_semi = c->out_layout;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_semi))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", out_semi))) return rc;
   if (in->width != out->width || in->height != out->height)
     return fail(c, H2S_E_INVALID_ARG, "input and output frame sizes differ");
   if (nframes == 0) return 0;
@@ -1624,11 +1661,11 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
     const size_t ib = host_in ? frame_bytes(in) * nframes : 0, ob = host_out ? frame_bytes(out) * nframes : 0;
     const size_t need = ((ib + 255) / 256) * 256 + ob;
     if ((rc = c->d_stage.reserve(c, need, "staging"))) return rc;
-    if (host_in) din = tight(in, c->d_stage);
-    if (host_out) dout = tight(out, c->d_stage + ((ib + 255) / 256) * 256);
+    if (host_in) din = tight(in, c->d_stage, in_semi);
+    if (host_out) dout = tight(out, c->d_stage + ((ib + 255) / 256) * 256, out_semi);
   }
-  fill_geometry(&k, &din, &dout, nframes);
-  const bool vec = vec_ok(&din, false) && vec_ok(&dout, out8);
+  fill_geometry(&k, &din, &dout, nframes, in_semi, out_semi);
+  const bool vec = vec_ok(&din, false, in_semi) && vec_ok(&dout, out8, out_semi);
   // fast path: the tile kernel over whole 64 x 32 tiles; the generic kernel
   // covers the rest (choose_path / fast_params_ok) and the ragged columns
   const int path = choose_path(c, k, &din, &dout, out8);
@@ -1650,7 +1687,7 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   if ((host_in || host_out) && nframes > 1 && !c->serial_host)
     return process_pipelined(c, k, in, out, din, dout, nframes, fast, vec, out8, s, dyn_peak);
   if (host_in) {
-    hipError_t e = copy_frames(&din, in, nframes, s);
+    hipError_t e = copy_frames(&din, in, nframes, s, in_semi);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "host->device copy"));
   }
   timing_begin(c, s);
@@ -1668,7 +1705,7 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "kernel launch"));
   timing_end(c, s);
   if (host_out) {
-    e = copy_frames(out, &dout, nframes, s);
+    e = copy_frames(out, &dout, nframes, s, out_semi);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "device->host copy"));
   }
   if (two_pass && (rc = c->chr_use.mark(c, s, "two-pass event"))) return queued_exit(c, s, rc);
@@ -1688,7 +1725,7 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input"))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t npx = (size_t)in->width * in->height, ob = npx * 3 * sizeof(float);
@@ -1704,12 +1741,12 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   h2s_frames din = *in;
   hipError_t e;
   if (in->location == H2S_LOC_HOST) {
-    din = tight(in, base);
-    if ((e = copy_frames(&din, in, 1, s)) != hipSuccess) return hip_fail(c, e, "debug copy");
+    din = tight(in, base, c->in_layout);
+    if ((e = copy_frames(&din, in, 1, s, c->in_layout)) != hipSuccess) return hip_fail(c, e, "debug copy");
   }
   fo = tight(&fo, base + ib);
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
-  fill_geometry(&k, &din, &fo, 1);
+  fill_geometry(&k, &din, &fo, 1, c->in_layout, 0);   // (fo: the call's own planar scratch frame)
   const bool out8 = c->params.bits_out == 8;
   const int path = choose_path(c, k, &din, &fo, out8);
   // the generic debug kernel covers every pixel; on the tile path the tile
@@ -1766,18 +1803,28 @@ int h2s_set_option(h2s_ctx* c, int key, int64_t value) {
   }
 }
 
+int h2s_set_frame_layout(h2s_ctx* c, int in_layout, int out_layout) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  auto known = [](int l) { return l == H2S_LAYOUT_PLANAR || l == H2S_LAYOUT_SEMI; };
+  if (!known(in_layout) || !known(out_layout)) return fail(c, H2S_E_INVALID_ARG, "unknown frame layout");
+  // (only the arguments of later launches change: nothing queued reads these)
+  c->in_layout = in_layout, c->out_layout = out_layout;
+  return 0;
+}
+
 int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input"))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output"))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_layout))) return rc;
   // host sets are staged into tight device copies, whose alignment decides
   h2s_frames din = *in, dout = *out;
   uint8_t* fake = (uint8_t*)(uintptr_t)4096;
-  if (in->location == H2S_LOC_HOST) din = tight(in, fake);
-  if (out->location == H2S_LOC_HOST) dout = tight(out, fake);
+  if (in->location == H2S_LOC_HOST) din = tight(in, fake, c->in_layout);
+  if (out->location == H2S_LOC_HOST) dout = tight(out, fake, c->out_layout);
+  fill_geometry(&k, &din, &dout, 1, c->in_layout, c->out_layout);
   return choose_path(c, k, &din, &dout, c->params.bits_out == 8);
 }
 
@@ -1838,8 +1885,16 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
   if (!c->params_set) return fail(c, H2S_E_INVALID_ARG, "h2s_set_params was not called");
   if (c->params.bits_out != 8)
     return fail(c, H2S_E_INVALID_ARG, "preview needs params.bits_out == 8 (the chain's yuv420p)");
-  int rc = check_frames(c, in, c->params.bits_in, "input");
+  int rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout);
   if (rc) return rc;
+  // the chain's output here is the call's own yuv420p scratch: planar, whatever
+  // layout the context writes its callers' frames in
+  struct PlanarOut {
+    h2s_ctx* c;
+    int saved;
+    explicit PlanarOut(h2s_ctx* c_) : c(c_), saved(c_->out_layout) { c->out_layout = H2S_LAYOUT_PLANAR; }
+    ~PlanarOut() { c->out_layout = saved; }
+  } planar_out(c);
   const int W = in->width, H = in->height;
   const bool scale = out_w != W || out_h != H;
   if (scale && (out_w > 4 * 8192 || out_h > 4 * 8192 || (double)W / out_w > 12.0 || (double)H / out_h > 12.0))
@@ -1919,7 +1974,7 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
     for (int f = 0; f < nframes; f++) {
       h2s_frames fi = *in, fo = y8;
       for (int k = 0; k < 3; k++) {
-        fi.data[k] = (uint8_t*)in->data[k] + (long long)f * in->frame_pitch[k];
+        if (in->data[k]) fi.data[k] = (uint8_t*)in->data[k] + (long long)f * in->frame_pitch[k];
         fo.data[k] = (uint8_t*)y8.data[k] + (long long)f * y8.frame_pitch[k];
       }
       if ((e = hipMemsetAsync(c->d_pk, 0, pb, s)) != hipSuccess)

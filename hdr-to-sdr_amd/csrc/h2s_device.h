@@ -25,6 +25,12 @@ struct KParams {
   long long in_ls[3], in_fp[3];
   uint8_t* out[3];
   long long out_ls[3], out_fp[3];
+  // frame layout (h2s_set_frame_layout).  Semi-planar: plane 2 aliases plane
+  // 1 one sample on (same linesize and pitch), samples of a chroma row lie
+  // cstep samples apart, and 16-bit words carry the code in the high bits:
+  // code = word >> in_sh (in_mask then drops the word's wrapped-down bits),
+  // word = code << out_sh.  Planar: cstep 1, shifts 0
+  int in_cstep, in_sh, out_cstep, out_sh;
   // S1: zimg depth conversion, BT.2020-NCL matrix, transfer
   float y_scale, y_off, c_scale, c_off;
   float m_rcr, m_gcb, m_gcr, m_bcb;
@@ -232,6 +238,14 @@ struct FastParams : CurveConsts {
   int dbg_w;
   const float4* dbg_lut;
   float inv_nm1;
+  // semi-planar surfaces (h2s_set_frame_layout), read by the k_tile<..., SEMI>
+  // instances only (block-uniform branches there; the planar instances never
+  // touch these, and they sit last so that no other field moves): plane 1
+  // holds (Cb, Cr) pairs and plane 2 is unused; 16-bit words carry the code
+  // in the high bits.  Input words are shifted down by in_sh and masked with
+  // in_mask2 (which then also clears the bits that cross the halves of a word
+  // pair); output codes are shifted up by out_sh
+  int in_semi, in_sh, out_semi, out_sh;
 };
 
 constexpr int TBW = 64, TBH = 32;   // k_tile: luma tile of one block
@@ -688,8 +702,9 @@ __device__ __forceinline__ int quant_o(float v, float off, int qmax) {
 
 // S8 expansion of a quantised code to the output depth
 __device__ __forceinline__ int expand_code(const KParams& P, int v) {
-  if (!P.shift_out) return v;
-  return P.expand_rep ? (v << P.shift_out) | (v >> (8 - P.shift_out)) : v << P.shift_out;
+  // (out_sh: a semi-planar 16-bit word carries the code in its high bits)
+  if (!P.shift_out) return v << P.out_sh;
+  return (P.expand_rep ? (v << P.shift_out) | (v >> (8 - P.shift_out)) : v << P.shift_out) << P.out_sh;
 }
 
 }  // namespace h2s

@@ -6,18 +6,31 @@
 
 namespace h2s {
 
-H2S_TILE_INSTANCE(0, 0)
-H2S_TILE_EXTERN(0, 1)   // h2s_fast_lp.hip
-H2S_TILE_EXTERN(1, 0)
-H2S_TILE_EXTERN(1, 1)
-H2S_TILE_EXTERN(2, 0)
-H2S_TILE_EXTERN(2, 1)
-H2S_TILE_EXTERN(3, 0)
-H2S_TILE_EXTERN(3, 1)
-H2S_TILE_EXTERN(4, 0)
-H2S_TILE_EXTERN(4, 1)
-H2S_TILE_EXTERN(5, 0)
-H2S_TILE_EXTERN(5, 1)
+H2S_TILE_INSTANCE(0, 0, false)
+H2S_TILE_EXTERN(0, 1, false)   // h2s_fast_lp.hip
+H2S_TILE_EXTERN(1, 0, false)
+H2S_TILE_EXTERN(1, 1, false)
+H2S_TILE_EXTERN(2, 0, false)
+H2S_TILE_EXTERN(2, 1, false)
+H2S_TILE_EXTERN(3, 0, false)
+H2S_TILE_EXTERN(3, 1, false)
+H2S_TILE_EXTERN(4, 0, false)
+H2S_TILE_EXTERN(4, 1, false)
+H2S_TILE_EXTERN(5, 0, false)
+H2S_TILE_EXTERN(5, 1, false)
+// the instances for semi-planar frame sets (h2s_fast_semi*.hip)
+H2S_TILE_EXTERN(0, 0, true)
+H2S_TILE_EXTERN(0, 1, true)
+H2S_TILE_EXTERN(1, 0, true)
+H2S_TILE_EXTERN(1, 1, true)
+H2S_TILE_EXTERN(2, 0, true)
+H2S_TILE_EXTERN(2, 1, true)
+H2S_TILE_EXTERN(3, 0, true)
+H2S_TILE_EXTERN(3, 1, true)
+H2S_TILE_EXTERN(4, 0, true)
+H2S_TILE_EXTERN(4, 1, true)
+H2S_TILE_EXTERN(5, 0, true)
+H2S_TILE_EXTERN(5, 1, true)
 
 // YUV-premultiplied lattice (12-byte records, .cube order):
 // ((16 + 219*Y)*s + 0.5, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
@@ -57,8 +70,14 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   // profiles/r03/ablations/blocks_per_cu.log)
   const size_t lds = ((size_t)F.eq_n * sizeof(uint16_t) + 15) & ~(size_t)15;
   if (tm == 7 || tm == 8 || lp) desat = 0;
-#define H2S_DISPATCH(D) \
-  return lp ? launch_tile<D, 1>(F, trc, tm, desat, grid, lds, s) : launch_tile<D, 0>(F, trc, tm, desat, grid, lds, s)
+  // planar sets on both sides: the instances without the layout branches
+  const bool semi = F.in_semi || F.out_semi;
+#define H2S_DISPATCH(D)                                                                                  \
+  if (semi)                                                                                              \
+    return lp ? launch_tile<D, 1, true>(F, trc, tm, desat, grid, lds, s)                                 \
+              : launch_tile<D, 0, true>(F, trc, tm, desat, grid, lds, s);                                \
+  return lp ? launch_tile<D, 1, false>(F, trc, tm, desat, grid, lds, s)                                  \
+            : launch_tile<D, 0, false>(F, trc, tm, desat, grid, lds, s)
   switch (dbg) {
     case 0: H2S_DISPATCH(0);
     case 1: H2S_DISPATCH(1);

@@ -6,11 +6,11 @@
 
 namespace h2s {
 
-H2S_TILE_INSTANCE(3, 0)
-H2S_TILE_INSTANCE(3, 1)
-H2S_TILE_INSTANCE(4, 0)
-H2S_TILE_INSTANCE(4, 1)
-H2S_TILE_INSTANCE(5, 0)
-H2S_TILE_INSTANCE(5, 1)
+H2S_TILE_INSTANCE(3, 0, false)
+H2S_TILE_INSTANCE(3, 1, false)
+H2S_TILE_INSTANCE(4, 0, false)
+H2S_TILE_INSTANCE(4, 1, false)
+H2S_TILE_INSTANCE(5, 0, false)
+H2S_TILE_INSTANCE(5, 1, false)
 
 }  // namespace h2s

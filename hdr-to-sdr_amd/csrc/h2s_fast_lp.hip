@@ -9,6 +9,6 @@
 
 namespace h2s {
 
-H2S_TILE_INSTANCE(0, 1)
+H2S_TILE_INSTANCE(0, 1, false)
 
 }  // namespace h2s

@@ -31,6 +31,14 @@ __device__ __forceinline__ long long xcd_remap(long long b, long long nb) {
 __device__ __forceinline__ int ld16(const uint8_t* row, int x) {
   return *reinterpret_cast<const uint16_t*>(row + 2 * x);
 }
+// the input code of a 16-bit word (semi-planar: in its high bits), masked
+// (h2s_lp_p010 TRUNCATE; the mask also bounds a semi-planar code)
+__device__ __forceinline__ int code_of(const KParams& P, unsigned w16) { return (int)((w16 >> P.in_sh) & P.in_mask); }
+// luma sample x / chroma sample x (P.in_cstep words apart) of a row
+__device__ __forceinline__ int ldy(const KParams& P, const uint8_t* row, int x) { return code_of(P, (unsigned)ld16(row, x)); }
+__device__ __forceinline__ int ldc(const KParams& P, const uint8_t* row, int x) {
+  return code_of(P, (unsigned)ld16(row, x * P.in_cstep));
+}
 
 // C444: BICUBIC chroma (two-pass path): store every pixel's (Cb, Cr) into
 // P.chr444 (frame 0 of the launch, W x H) instead of the 2x2 mean; the
@@ -53,22 +61,28 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
     const uint8_t* ru = P.in[1] + f * P.in_fp[1] + crow[i] * P.in_ls[1];
     const uint8_t* rv = P.in[2] + f * P.in_fp[2] + crow[i] * P.in_ls[2];
     if (VEC && full && QPT == 4) {
-      const uint2 a = *reinterpret_cast<const uint2*>(ru + 2 * cx0);
-      const uint2 b = *reinterpret_cast<const uint2*>(rv + 2 * cx0);
       const int hx = edge(P, cx0 + 4, cw);
-      const int m = (int)P.in_mask;   // h2s_lp_p010 TRUNCATE drops the two low bits
-      int su[5] = {(int)(a.x & 0xffff) & m, (int)(a.x >> 16) & m, (int)(a.y & 0xffff) & m, (int)(a.y >> 16) & m,
-                   ld16(ru, hx) & m};
-      int sv[5] = {(int)(b.x & 0xffff) & m, (int)(b.x >> 16) & m, (int)(b.y & 0xffff) & m, (int)(b.y >> 16) & m,
-                   ld16(rv, hx) & m};
+      if (P.in_cstep == 2) {   // semi-planar: four (Cb, Cr) pairs in one 16-byte load
+        const uint4 q = *reinterpret_cast<const uint4*>(ru + 4 * cx0);
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-      for (int k = 0; k <= QPT; k++) ccu[i][k] = su[k], ccv[i][k] = sv[k];
+        for (int k = 0; k < 4; k++) ccu[i][k] = code_of(P, w[k] & 0xffff), ccv[i][k] = code_of(P, w[k] >> 16);
+      } else {
+        const uint2 a = *reinterpret_cast<const uint2*>(ru + 2 * cx0);
+        const uint2 b = *reinterpret_cast<const uint2*>(rv + 2 * cx0);
+        // (code_of: h2s_lp_p010 TRUNCATE drops the two low bits)
+        const unsigned su[4] = {a.x & 0xffff, a.x >> 16, a.y & 0xffff, a.y >> 16};
+        const unsigned sv[4] = {b.x & 0xffff, b.x >> 16, b.y & 0xffff, b.y >> 16};
+#pragma unroll
+        for (int k = 0; k < 4; k++) ccu[i][k] = code_of(P, su[k]), ccv[i][k] = code_of(P, sv[k]);
+      }
+      ccu[i][4] = ldc(P, ru, hx), ccv[i][4] = ldc(P, rv, hx);
     } else {
 #pragma unroll
       for (int k = 0; k <= QPT; k++) {
         const int x = edge(P, cx0 + k, cw);
-        ccu[i][k] = ld16(ru, x) & (int)P.in_mask;
-        ccv[i][k] = ld16(rv, x) & (int)P.in_mask;
+        ccu[i][k] = ldc(P, ru, x);
+        ccv[i][k] = ldc(P, rv, x);
       }
     }
 #pragma unroll
@@ -100,14 +114,14 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
       const unsigned w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        ys[j][2 * k] = (int)(w[k] & 0xffff & P.in_mask);
-        ys[j][2 * k + 1] = (int)((w[k] >> 16) & P.in_mask);
+        ys[j][2 * k] = code_of(P, w[k] & 0xffff);
+        ys[j][2 * k + 1] = code_of(P, w[k] >> 16);
       }
     } else {
 #pragma unroll
       for (int k = 0; k < 2 * QPT; k++) {
         const int x = x0 + k < P.W ? x0 + k : P.W - 1;
-        ys[j][k] = ld16(ry, x) & (int)P.in_mask;
+        ys[j][k] = ldy(P, ry, x);
       }
     }
   }
@@ -185,7 +199,21 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   if (C444) return;
   uint8_t* ru = P.out[1] + f * P.out_fp[1] + cy * P.out_ls[1];
   uint8_t* rv = P.out[2] + f * P.out_fp[2] + cy * P.out_ls[2];
-  if (VEC && full && QPT == 4) {
+  if (VEC && full && QPT == 4 && P.out_cstep == 2) {   // semi-planar: the four (Cb, Cr) pairs in one store
+    if (OUT8) {
+      uint2 a;
+      a.x = (unsigned)uo[0] | ((unsigned)vo[0] << 8) | ((unsigned)uo[1] << 16) | ((unsigned)vo[1] << 24);
+      a.y = (unsigned)uo[2] | ((unsigned)vo[2] << 8) | ((unsigned)uo[3] << 16) | ((unsigned)vo[3] << 24);
+      *reinterpret_cast<uint2*>(ru + 2 * cx0) = a;
+    } else {
+      uint4 a;
+      a.x = (unsigned)uo[0] | ((unsigned)vo[0] << 16);
+      a.y = (unsigned)uo[1] | ((unsigned)vo[1] << 16);
+      a.z = (unsigned)uo[2] | ((unsigned)vo[2] << 16);
+      a.w = (unsigned)uo[3] | ((unsigned)vo[3] << 16);
+      *reinterpret_cast<uint4*>(ru + 4 * cx0) = a;
+    }
+  } else if (VEC && full && QPT == 4) {
     if (OUT8) {
       *reinterpret_cast<unsigned*>(ru + cx0) =
           (unsigned)uo[0] | ((unsigned)uo[1] << 8) | ((unsigned)uo[2] << 16) | ((unsigned)uo[3] << 24);
@@ -204,12 +232,13 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
 #pragma unroll
     for (int k = 0; k < QPT; k++) {
       if (cx0 + k < cw) {
+        const int xo = (cx0 + k) * P.out_cstep;
         if (OUT8) {
-          ru[cx0 + k] = (uint8_t)uo[k];
-          rv[cx0 + k] = (uint8_t)vo[k];
+          ru[xo] = (uint8_t)uo[k];
+          rv[xo] = (uint8_t)vo[k];
         } else {
-          reinterpret_cast<uint16_t*>(ru)[cx0 + k] = (uint16_t)uo[k];
-          reinterpret_cast<uint16_t*>(rv)[cx0 + k] = (uint16_t)vo[k];
+          reinterpret_cast<uint16_t*>(ru)[xo] = (uint16_t)uo[k];
+          reinterpret_cast<uint16_t*>(rv)[xo] = (uint16_t)vo[k];
         }
       }
     }
@@ -242,9 +271,9 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
   auto hpass = [&](int plane, int cyy) -> float {
     const uint8_t* row = P.in[plane] + edge(P, cyy, ch) * P.in_ls[plane];
     const int k = x >> 1;
-    const float a = (float)(ld16(row, edge(P, k, cw)) & (int)P.in_mask) * P.c_scale + P.c_off;
+    const float a = (float)ldc(P, row, edge(P, k, cw)) * P.c_scale + P.c_off;
     if (!(x & 1)) return a;
-    const float b = (float)(ld16(row, edge(P, k + 1, cw)) & (int)P.in_mask) * P.c_scale + P.c_off;
+    const float b = (float)ldc(P, row, edge(P, k + 1, cw)) * P.c_scale + P.c_off;
     return 0.5f * a + 0.5f * b;
   };
   auto up = [&](int plane) -> float {
@@ -253,16 +282,16 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
     return 0.75f * hpass(plane, m) + 0.25f * hpass(plane, m + 1);
   };
   const float cb = up(1), cr = up(2);
-  const int ycode = ld16(P.in[0] + y * P.in_ls[0], x) & (int)P.in_mask;
+  const int ycode = ldy(P, P.in[0] + y * P.in_ls[0], x);
   const float yv = (float)ycode * P.y_scale + P.y_off;
   float r, g, b;
   if (P.pipe == PIPE_LIBPLACEBO) {   // the exact path (h2s_lpx.h), as k_process<..., LPX>
     auto hpd = [&](int plane, int cyy) -> double {
       const uint8_t* row = P.in[plane] + edge(P, cyy, ch) * P.in_ls[plane];
       const int k = x >> 1;
-      const double a = lpx_chroma(P, ld16(row, edge(P, k, cw)) & (int)P.in_mask);
+      const double a = lpx_chroma(P, ldc(P, row, edge(P, k, cw)));
       if (!(x & 1)) return a;
-      return 0.5 * (a + lpx_chroma(P, ld16(row, edge(P, k + 1, cw)) & (int)P.in_mask));
+      return 0.5 * (a + lpx_chroma(P, ldc(P, row, edge(P, k + 1, cw))));
     };
     auto upd = [&](int plane) -> double {
       const int m = y >> 1;
@@ -317,11 +346,12 @@ __global__ __launch_bounds__(256) void k_chroma_bicubic(const KParams P, const C
   const int v = expand_code(P, quant_o((128.0f + 224.0f * sv) * P.qscale, co, P.qmax));
   uint8_t* ru = P.out[1] + m * P.out_ls[1];
   uint8_t* rv = P.out[2] + m * P.out_ls[2];
+  const int xo = k * P.out_cstep;   // (semi-planar: plane 2 aliases plane 1 one sample on)
   if (OUT8) {
-    ru[k] = (uint8_t)u, rv[k] = (uint8_t)v;
+    ru[xo] = (uint8_t)u, rv[xo] = (uint8_t)v;
   } else {
-    reinterpret_cast<uint16_t*>(ru)[k] = (uint16_t)u;
-    reinterpret_cast<uint16_t*>(rv)[k] = (uint16_t)v;
+    reinterpret_cast<uint16_t*>(ru)[xo] = (uint16_t)u;
+    reinterpret_cast<uint16_t*>(rv)[xo] = (uint16_t)v;
   }
 }
 
@@ -419,7 +449,7 @@ hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float
 // one pixel's PQ-domain max(R,G,B) from its integer codes (nearest chroma)
 template <int TRC>
 __device__ __forceinline__ float peak_px(const KParams& P, unsigned yc, unsigned uc, unsigned vc) {
-  yc &= P.in_mask, uc &= P.in_mask, vc &= P.in_mask;
+  yc = (yc >> P.in_sh) & P.in_mask, uc = (uc >> P.in_sh) & P.in_mask, vc = (vc >> P.in_sh) & P.in_mask;   // code_of
   const float Y = (float)yc * P.y_scale + P.y_off;
   const float cb = (float)uc * P.c_scale + P.c_off, cr = (float)vc * P.c_scale + P.c_off;
   const float er = Y + P.m_rcr * cr, eg = Y + P.m_gcb * cb + P.m_gcr * cr, eb = Y + P.m_bcb * cb;
@@ -638,7 +668,8 @@ __global__ __launch_bounds__(256) void k_peak_stats(const KParams P, float2* par
     const uint16_t* vr = reinterpret_cast<const uint16_t*>(P.in[2] + f * P.in_fp[2] + (y >> 1) * P.in_ls[2]);
     float rs = 0.0f;
     for (int x = threadIdx.x; x < P.W; x += blockDim.x) {
-      const float m = peak_px<TRC>(P, yr[x], ur[x >> 1], vr[x >> 1]);
+      const int xc = (x >> 1) * P.in_cstep;   // (semi-planar: vr = ur + 1, pairs two words apart)
+      const float m = peak_px<TRC>(P, yr[x], ur[xc], vr[xc]);
       mx = fmaxf(mx, m);
       rs += m;
       if (HIST) run.add(lh, m);
@@ -680,12 +711,22 @@ __global__ __launch_bounds__(256) void k_peak_stats_v(const KParams P, float2* p
   auto load = [&](int i, Chunk& c) {
     const int r = i / cpr, cx = i - r * cpr;
     c.ya = reinterpret_cast<const uint4*>(y0 + r * P.in_ls[0])[cx];
-    c.ua = reinterpret_cast<const uint2*>(u0 + (r >> 1) * P.in_ls[1])[cx];
-    c.va = reinterpret_cast<const uint2*>(v0 + (r >> 1) * P.in_ls[2])[cx];
+    if (P.in_cstep == 2) {   // semi-planar: the chunk's four (Cb, Cr) pairs, 16 bytes of plane 1
+      const uint2* q = reinterpret_cast<const uint2*>(u0 + (r >> 1) * P.in_ls[1]) + 2 * cx;
+      c.ua = q[0], c.va = q[1];
+    } else {
+      c.ua = reinterpret_cast<const uint2*>(u0 + (r >> 1) * P.in_ls[1])[cx];
+      c.va = reinterpret_cast<const uint2*>(v0 + (r >> 1) * P.in_ls[2])[cx];
+    }
   };
   auto fold = [&](const Chunk& c) {
-    const unsigned uu[4] = {c.ua.x & 0xffff, c.ua.x >> 16, c.ua.y & 0xffff, c.ua.y >> 16};
-    const unsigned vv[4] = {c.va.x & 0xffff, c.va.x >> 16, c.va.y & 0xffff, c.va.y >> 16};
+    unsigned uu[4] = {c.ua.x & 0xffff, c.ua.x >> 16, c.ua.y & 0xffff, c.ua.y >> 16};
+    unsigned vv[4] = {c.va.x & 0xffff, c.va.x >> 16, c.va.y & 0xffff, c.va.y >> 16};
+    if (P.in_cstep == 2) {   // pairs: word k = (Cb k, Cr k)
+      const unsigned w[4] = {c.ua.x, c.ua.y, c.va.x, c.va.y};
+#pragma unroll
+      for (int k = 0; k < 4; k++) uu[k] = w[k] & 0xffff, vv[k] = w[k] >> 16;
+    }
     const unsigned yy[8] = {c.ya.x & 0xffff, c.ya.x >> 16, c.ya.y & 0xffff, c.ya.y >> 16,
                             c.ya.z & 0xffff, c.ya.z >> 16, c.ya.w & 0xffff, c.ya.w >> 16};
     float rs = 0.0f;
@@ -744,6 +785,7 @@ __global__ __launch_bounds__(256) void k_peak_stats_q(const KParams P, float2* p
   const uint8_t* u0 = P.in[1] + f * P.in_fp[1];
   const uint8_t* v0 = P.in[2] + f * P.in_fp[2];
   const unsigned m2 = P.in_mask | (P.in_mask << 16);
+  const int sh = P.in_sh;   // semi-planar: codes in the words' high bits (m2 clears what crosses the halves)
   const float ys = P.y_scale, yo = P.y_off, cs = P.c_scale, co = P.c_off;
   float mx = 0.0f, sm = 0.0f;
   HistRun run;
@@ -752,8 +794,13 @@ __global__ __launch_bounds__(256) void k_peak_stats_q(const KParams P, float2* p
   };
   auto load = [&](int i, Unit& q) {
     const int r = i / cpr, cx = i - r * cpr;
-    q.u = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 16 * cx);
-    q.v = *reinterpret_cast<const uint4*>(v0 + r * P.in_ls[2] + 16 * cx);
+    if (P.in_cstep == 2) {   // semi-planar: the unit's eight (Cb, Cr) pairs, 32 bytes of plane 1
+      q.u = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 32 * cx);
+      q.v = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 32 * cx + 16);
+    } else {
+      q.u = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 16 * cx);
+      q.v = *reinterpret_cast<const uint4*>(v0 + r * P.in_ls[2] + 16 * cx);
+    }
     const uint4* ya = reinterpret_cast<const uint4*>(y0 + 2 * r * P.in_ls[0] + 32 * cx);
     const uint4* yb = reinterpret_cast<const uint4*>(y0 + (2 * r + 1) * P.in_ls[0] + 32 * cx);
     q.y0a = ya[0], q.y0b = ya[1], q.y1a = yb[0], q.y1b = yb[1];
@@ -763,7 +810,7 @@ __global__ __launch_bounds__(256) void k_peak_stats_q(const KParams P, float2* p
     const uint4 rows[4] = {q.y0a, q.y0b, q.y1a, q.y1b};
 #pragma unroll
     for (int h = 0; h < 4; h++) {
-      const unsigned w[4] = {rows[h].x & m2, rows[h].y & m2, rows[h].z & m2, rows[h].w & m2};
+      const unsigned w[4] = {(rows[h].x >> sh) & m2, (rows[h].y >> sh) & m2, (rows[h].z >> sh) & m2, (rows[h].w >> sh) & m2};
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const unsigned code = (k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xffffu;
@@ -772,8 +819,16 @@ __global__ __launch_bounds__(256) void k_peak_stats_q(const KParams P, float2* p
     }
   };
   auto fold = [&](const Unit& q) {
-    const unsigned ua[4] = {q.u.x & m2, q.u.y & m2, q.u.z & m2, q.u.w & m2};
-    const unsigned va[4] = {q.v.x & m2, q.v.y & m2, q.v.z & m2, q.v.w & m2};
+    unsigned ua[4] = {(q.u.x >> sh) & m2, (q.u.y >> sh) & m2, (q.u.z >> sh) & m2, (q.u.w >> sh) & m2};
+    unsigned va[4] = {(q.v.x >> sh) & m2, (q.v.y >> sh) & m2, (q.v.z >> sh) & m2, (q.v.w >> sh) & m2};
+    if (P.in_cstep == 2) {   // pairs (word k = Cb k | Cr k << 16) -> the planar words (block-uniform)
+      const unsigned p[8] = {ua[0], ua[1], ua[2], ua[3], va[0], va[1], va[2], va[3]};
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        ua[i] = (p[2 * i] & 0xffffu) | (p[2 * i + 1] << 16);
+        va[i] = (p[2 * i] >> 16) | (p[2 * i + 1] & 0xffff0000u);
+      }
+    }
     float d[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -828,10 +883,12 @@ hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& 
   if (P.nframes <= 0) return hipSuccess;
   const dim3 grid(T.M.nblocks, P.nframes);
   auto al = [](long long v, int a) { return (v & (a - 1)) == 0; };
+  // (semi-planar: plane 2 is plane 1 one sample on, and is not loaded from)
   auto planes_al = [&](int ya, int ca) {
     return al((long long)(uintptr_t)P.in[0], ya) && al(P.in_ls[0], ya) && al(P.in_fp[0], ya) &&
            al((long long)(uintptr_t)P.in[1], ca) && al(P.in_ls[1], ca) && al(P.in_fp[1], ca) &&
-           al((long long)(uintptr_t)P.in[2], ca) && al(P.in_ls[2], ca) && al(P.in_fp[2], ca);
+           (P.in_cstep == 2 ||
+            (al((long long)(uintptr_t)P.in[2], ca) && al(P.in_ls[2], ca) && al(P.in_fp[2], ca)));
   };
   const bool vec = P.W % 8 == 0 && planes_al(16, 8);
   const bool quad = P.W % 16 == 0 && P.transfer == 0 && T.form != 1 && planes_al(16, 16);

@@ -818,9 +818,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const uint8_t* base
 }
 
 // one tile's global loads, held in registers between issue and the LDS commit
+// (semi-planar input, F.in_semi: ua = four (Cb, Cr) pairs of the interleaved
+// plane on threads t < 144, uh = the pair right of them; the same registers)
+template <bool SEMI>
 struct TileRegs {
   uint4 ya, ua;     // luma chunk; chroma chunk of plane pc (threads tc < 72)
-  uint16_t uh;      // the chroma chunk's right-halo sample
+  std::conditional_t<SEMI, unsigned, uint16_t> uh;   // the chroma chunk's right-halo sample (SEMI: or pair)
 };
 
 struct TileGeo {
@@ -868,15 +871,19 @@ struct LaneOfs {
   int sy, sc;      // stores: luma row / 8-sample chunk; chroma row of plane pl
 };
 
+template <bool SEMI>
 __device__ __forceinline__ LaneOfs lane_ofs(const FastParams& F, int t) {
   LaneOfs L;
   L.y = (t >> 3) * (int)F.in_ls[0] + 16 * (t & 7);
   const int pc = (t >> 7) & 1, tc = t & 127;
   L.u = (tc >> 2) * (int)F.in_ls[1 + pc] + 16 * (tc & 3);
+  // semi-planar: chroma row t >> 3, 16-byte chunk t & 7 (four pairs) of the interleaved plane
+  if (SEMI && F.in_semi) L.u = (t >> 3) * (int)F.in_ls[1] + 16 * (t & 7);
   const int sb = F.out8 ? 8 : 16;
   L.sy = (t >> 3) * (int)F.out_ls[0] + sb * (t & 7);
   const int pl = (t >> 6) & 1, rem = t & 63;
   L.sc = (rem >> 2) * (int)F.out_ls[1 + pl] + sb * (rem & 3);
+  if (SEMI && F.out_semi) L.sc = (t >> 3) * (int)F.out_ls[1] + sb * (t & 7);
   return L;
 }
 
@@ -888,14 +895,15 @@ __device__ __forceinline__ LaneOfs lane_ofs(const FastParams& F, int t) {
 // halo) lie inside the frame take the lane offsets of LaneOfs plus a scalar
 // origin; border tiles clamp per lane.  The chroma registers of threads >= 72
 // are left undefined (never committed).
-__device__ __forceinline__ TileRegs tile_load(const FastParams& F, const TileGeo& g, int t, const LaneOfs& L) {
+template <bool SEMI>
+__device__ __forceinline__ TileRegs<SEMI> tile_load(const FastParams& F, const TileGeo& g, int t, const LaneOfs& L) {
   // Every thread issues exactly one load of each kind whatever the tile: the
   // offsets are chosen per case and the loads follow the merge; threads
   // without a chroma chunk read out of range, which returns 0 and fetches
   // nothing
   const __amdgpu_buffer_rsrc_t iy = plane_rsrc(F.in[0] + g.f * F.in_fp[0], F.in_bytes[0]);
   const int yr = t >> 3, yc = t & 7;
-  TileRegs r;
+  TileRegs<SEMI> r;
   int vy, sy;
   if (g.py0 + TBH <= F.H) {   // block-uniform
     vy = L.y, sy = g.py0 * (int)F.in_ls[0] + 2 * g.px0;
@@ -903,6 +911,27 @@ __device__ __forceinline__ TileRegs tile_load(const FastParams& F, const TileGeo
     vy = (g.py0 + yr < F.H ? g.py0 + yr : F.H - 1) * (int)F.in_ls[0] + 2 * (g.px0 + 8 * yc), sy = 0;
   }
   r.ya = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(iy, vy, sy, NT));
+  if (SEMI && F.in_semi) {   // block-uniform
+    // the interleaved plane: 18 rows x 8 chunks of four (Cb, Cr) pairs on
+    // threads 0..143, each with the pair right of its chunk (4 bytes), so
+    // every line of the plane is read once
+    const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1] + g.f * F.in_fp[1], F.in_bytes[1]);
+    const int ls = (int)F.in_ls[1];
+    int vc, vh, sc;
+    if (g.cy0 >= 1 && g.cy0 + CBH + 1 <= F.ch && g.cx0 + CBW + 1 <= F.cw) {   // block-uniform
+      vc = L.u, vh = L.u + 16, sc = (g.cy0 - 1) * ls + 4 * g.cx0;
+    } else {
+      const int clr = t >> 3, ccx = t & 7;
+      const int row = chroma_edge_at(g.cy0 - 1 + clr, F.ch, F.chroma_edge);
+      vc = row * ls + 4 * (g.cx0 + 4 * ccx);
+      vh = row * ls + 4 * chroma_edge_at(g.cx0 + 4 * ccx + 4, F.cw, F.chroma_edge);
+      sc = 0;
+    }
+    if (t >= 144) vc = vh = 0x7FFFFFF0;
+    r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ic, vc, sc, NT));
+    r.uh = __builtin_amdgcn_raw_buffer_load_b32(ic, vh, sc, 0);
+    return r;
+  }
   const int pc = __builtin_amdgcn_readfirstlane(t >> 7), tc = t & 127;
   const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1 + pc] + g.f * F.in_fp[1 + pc], F.in_bytes[1 + pc]);
   const int ls = (int)F.in_ls[1 + pc];
@@ -956,6 +985,29 @@ __device__ __forceinline__ float stage_chroma(float* plane, uint4 a, unsigned h,
   for (int k = 0; k < 4; k++)
     *reinterpret_cast<float4*>(d + 4 * k) =
         make_float4(v[2 * k] + v[2 * k], v[2 * k] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 2]);
+  return m;
+}
+// the same for a semi-planar chunk: a = four (Cb, Cr) pairs (Cb in the low
+// half of each word), h = the pair right of them, codes already shifted down
+// and masked; tt: row tt >> 3, 4-pair chunk tt & 7 of the tile's 18 x 8
+// chunks.  Both planes' rows leave in one call, same arithmetic per sample
+template <int HST>
+__device__ __forceinline__ float stage_chroma_semi(float* plane_u, float* plane_v, uint4 a, unsigned h, int tt, float cmid) {
+  const unsigned w[5] = {a.x, a.y, a.z, a.w, h};
+  float u[5], v[5];
+#pragma unroll
+  for (int k = 0; k < 5; k++) u[k] = (float)(w[k] & 0xffff) - cmid, v[k] = (float)(w[k] >> 16) - cmid;
+  float m = __builtin_fmaxf(fabsf(u[0]), fabsf(v[0]));
+#pragma unroll
+  for (int k = 1; k < 5; k++) m = __builtin_fmaxf(m, __builtin_fmaxf(fabsf(u[k]), fabsf(v[k])));
+  const int o = (tt >> 3) * HST + 8 * (tt & 7);
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    *reinterpret_cast<float4*>(plane_u + o + 4 * k) =
+        make_float4(u[2 * k] + u[2 * k], u[2 * k] + u[2 * k + 1], u[2 * k + 1] + u[2 * k + 1], u[2 * k + 1] + u[2 * k + 2]);
+    *reinterpret_cast<float4*>(plane_v + o + 4 * k) =
+        make_float4(v[2 * k] + v[2 * k], v[2 * k] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 2]);
+  }
   return m;
 }
 // luma codes of tile row r, chunk c (8 pixels), packed for one 16-byte (u16)
@@ -1013,6 +1065,44 @@ __device__ __forceinline__ void put_chroma(const FastParams& F, const TileGeo& g
     __builtin_amdgcn_raw_buffer_store_b128(v, oc_, vo, so + 2 * g.cx0, NTS);
 }
 
+// semi-planar output: row r, chunk c (four (Cb, Cr) pairs) of the tile's 16 x
+// 8 chunks, quantised as read_chroma, packed as pairs for one 16-byte store
+// (u16: the code in the word's high bits, F.out_sh) or 8-byte store (nv12: .xy)
+__device__ __forceinline__ u4v read_chroma_semi(const FastParams& F, const float* csum, int r, int c) {
+  const float4 vu = *reinterpret_cast<const float4*>(csum + r * CBW + 4 * c);
+  const float4 vv = *reinterpret_cast<const float4*>(csum + CBH * CBW + r * CBW + 4 * c);
+  const float s[8] = {vu.x, vv.x, vu.y, vv.y, vu.z, vv.z, vu.w, vv.w};
+  unsigned code[8];
+  if (F.dither) {   // sample (cx, cy) mod 8 = (4 (c & 1) + k / 2, r mod 8)
+#pragma unroll
+    for (int k = 0; k < 8; k++) code[k] = (unsigned)(int)(s[k] + (F.c_bias - 0.5f + dither_off(4 * (c & 1) + (k >> 1), r)));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) code[k] = (unsigned)(int)(s[k] + F.c_bias);
+  }
+  if (F.rep_rs == 31) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) code[k] <<= F.shift_out;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) code[k] = (code[k] << F.shift_out) | (code[k] >> F.rep_rs);
+  }
+  if (F.out8)
+    return u4v{code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24),
+               code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24), 0u, 0u};
+  return u4v{(code[0] | (code[1] << 16)) << F.out_sh, (code[2] | (code[3] << 16)) << F.out_sh,
+             (code[4] | (code[5] << 16)) << F.out_sh, (code[6] | (code[7] << 16)) << F.out_sh};
+}
+__device__ __forceinline__ void put_chroma_semi(const FastParams& F, const TileGeo& g, u4v v, int r, int vo) {
+  if (g.cy0 + r >= F.ch) return;
+  const __amdgpu_buffer_rsrc_t oc_ = plane_rsrc(F.out[1] + g.f * F.out_fp[1], F.out_bytes[1]);
+  const int so = g.cy0 * (int)F.out_ls[1];
+  if (F.out8)
+    __builtin_amdgcn_raw_buffer_store_b64(u2v{v.x, v.y}, oc_, vo, so + 2 * g.cx0, NTS);
+  else
+    __builtin_amdgcn_raw_buffer_store_b128(v, oc_, vo, so + 4 * g.cx0, NTS);
+}
+
 // Each block walks F.tpb consecutive tiles (XCD-remapped, so neighbouring
 // tiles and their lattice cells share one XCD's L2).  The loads of tile i+1
 // are issued before tile i is computed, so after the first tile the block no
@@ -1031,7 +1121,14 @@ __device__ __forceinline__ void put_chroma(const FastParams& F, const TileGeo& g
 // LP = 1: the libplacebo branch (src/utils.py:444-460, BT.2390 / spline):
 // BT.1886 encode against the target black, 8-bit rgba download, lut3d's 8-bit
 // path on plain R'G'B' records (truncating output), BT.709 Y'CbCr at depth q
-template <int TRC, int TM, int DESAT, int LP, int DBG = 0>
+// SEMI: the instances that also serve semi-planar frame sets (F.in_semi /
+// F.out_semi, h2s_set_frame_layout), with a block-uniform branch wherever the
+// addressing or the packing differs.  They are separate instances because
+// those branches cost registers whichever way they go (8-10 VGPRs and a dozen
+// spilled SGPRs on the product instances): a launch with
+// planar sets on both sides runs the SEMI = false instance, which compiles
+// to what it was before the layouts existed
+template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false>
 // 5 waves per SIMD = the LDS-bound occupancy (5 blocks of ~27.6 KB per CU;
 // 3, 4 and 6 measured slower on the bench content, 6 by 4.5 % in round 3 at
 // 80 VGPRs: profiles/r03/ablations/six_waves.log, blocks_per_cu.log): let
@@ -1069,8 +1166,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 
   // ---- prologue: first tile + tables, all issued before any wait ----
   TileGeo geo = tile_geo(F, tile);
-  const LaneOfs lofs = lane_ofs(F, t);
-  TileRegs cur = tile_load(F, geo, t, lofs);
+  const LaneOfs lofs = lane_ofs<SEMI>(F, t);
+  TileRegs<SEMI> cur = tile_load<SEMI>(F, geo, t, lofs);
   const __amdgpu_buffer_rsrc_t req = __builtin_amdgcn_make_buffer_rsrc((void*)F.eq_lut, (short)0, 2 * F.eq_n, 0x00020000);
   const unsigned eq0 = __builtin_amdgcn_raw_buffer_load_b16(req, 2 * t, 0, 0);  // out of range -> 0
   float4 pq0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1081,10 +1178,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   }
   // codes at the output depth: shift, or bit replication (h2s_expand;
   // rep_rs = 8 - shift, or 31 for a plain shift: the 8-bit code >> 31 = 0)
-  if (t < F.eq_n) eq_lds[t] = (uint16_t)((eq0 << F.shift_out) | (eq0 >> F.rep_rs));
+  // (semi-planar 16-bit output: the luma word's high-bit alignment, F.out_sh,
+  // is folded into the table, so the luma stores are the planar ones)
+  const int eq_sh = SEMI ? F.out_sh : 0;
+  if (t < F.eq_n) eq_lds[t] = (uint16_t)(((eq0 << F.shift_out) | (eq0 >> F.rep_rs)) << eq_sh);
   for (int i = t + 256; i < F.eq_n; i += 256) {  // native 10/12-bit tables
     const unsigned v = __builtin_amdgcn_raw_buffer_load_b16(req, 2 * i, 0, 0);
-    eq_lds[i] = (uint16_t)((v << F.shift_out) | (v >> F.rep_rs));
+    eq_lds[i] = (uint16_t)(((v << F.shift_out) | (v >> F.rep_rs)) << eq_sh);
   }
   // the first segment (E' < 1/128) marked (cubic FLT_MAX t: 0 at E = 0,
   // > DARK_MARK above) wherever the table is the PQ EOTF (not the CPU chain's
@@ -1253,26 +1353,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   auto mask_in = [&](uint4& a) {   // h2s_lp_p010 TRUNCATE (block-uniform)
     a.x &= F.in_mask2, a.y &= F.in_mask2, a.z &= F.in_mask2, a.w &= F.in_mask2;
   };
+  auto shift_in = [&](uint4& a) { a.x >>= F.in_sh, a.y >>= F.in_sh, a.z >>= F.in_sh, a.w >>= F.in_sh; };
 
   const int pl = __builtin_amdgcn_readfirstlane(t >> 6) & 1, rem = t & 63;   // chroma store role (t < 128)
   const bool cst = t < 128 && !F.chr444;
   for (;;) {
     H2S_MARK("tile: commit, prefetch");
     // ---- commit this tile's registers to LDS ----
-    if (F.in_mask2 != 0xFFFFFFFFu) {   // h2s_lp_p010 TRUNCATE (block-uniform)
+    if (F.in_mask2 != 0xFFFFFFFFu) {   // h2s_lp_p010 TRUNCATE, semi-planar words (block-uniform)
+      // semi-planar: the code sits in each 16-bit word's high bits; both
+      // halves of a pair move down together and the mask (always set then)
+      // clears what crossed from the high half, and the word's low junk bits
+      if constexpr (SEMI) {
+        if (F.in_sh) {
+          shift_in(cur.ya), shift_in(cur.ua);
+          cur.uh >>= F.in_sh;
+        }
+      }
       mask_in(cur.ya), mask_in(cur.ua);
       cur.uh &= F.in_mask2;
     }
     const float my = stage_luma<YST>(yin, cur.ya, t >> 3, t & 7, ysc, yoff);
     float mc = 0.0f;
-    if ((t & 127) < 72) mc = stage_chroma<HST>(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
+    if (SEMI && F.in_semi) {   // block-uniform
+      if (t < 144) mc = stage_chroma_semi<HST>(hrow[0], hrow[1], cur.ua, cur.uh, t, cmid);
+    } else if ((t & 127) < 72) {
+      mc = stage_chroma<HST>(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
+    }
     const int par = (int)(tile & 1u);
     if ((my > F.safe_y || mc > F.safe_c)) tflag[par] = 1;
     const TileGeo g = geo;
     const bool more = tile + 1 < tend;   // block-uniform
     if (more) {
       tile_next(F, geo);
-      cur = tile_load(F, geo, t, lofs);  // in flight during this tile's compute
+      cur = tile_load<SEMI>(F, geo, t, lofs);  // in flight during this tile's compute
     }
     __syncthreads();
     const bool fb = __builtin_amdgcn_readfirstlane(tflag[par]) == 0 && !F.chr444;
@@ -1286,7 +1400,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 
     // ---- write the tile: 16-byte (u16) / 8-byte (u8) non-temporal stores ----
     put_luma(F, g, read_luma<YST>(F, yin, t >> 3, t & 7), t >> 3, lofs.sy, 0);
-    if (cst) put_chroma(F, g, read_chroma(F, csum[0], pl, rem >> 2, rem & 3), pl, rem >> 2, lofs.sc);
+    if (cst) {
+      if (SEMI && F.out_semi)   // block-uniform
+        put_chroma_semi(F, g, read_chroma_semi(F, csum[0], t >> 3, t & 7), t >> 3, lofs.sc);
+      else
+        put_chroma(F, g, read_chroma(F, csum[0], pl, rem >> 2, rem & 3), pl, rem >> 2, lofs.sc);
+    }
     if (!more) break;
     ++tile;
     __syncthreads();   // the store phase has read yin / csum before they are refilled
@@ -1333,12 +1452,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 // branch), explicitly instantiated in exactly one .hip each: the two chains'
 // product instances compile in their own translation units, so each gets the
 // scheduler that measured fastest for it (_build.py SOURCE_FLAGS)
-template <int DBG, int LPI>
+template <int DBG, int LPI, bool SEMI = false>
 hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 grid, size_t lds, hipStream_t s) {
 #define X(T, M, D, L)                                                                       \
   if constexpr (L == LPI) {                                                                 \
     if (trc == T && tm == M && desat == D) {                                                \
-      hipLaunchKernelGGL((k_tile<T, M, D, L, DBG>), grid, dim3(256), lds, s, F);            \
+      hipLaunchKernelGGL((k_tile<T, M, D, L, DBG, SEMI>), grid, dim3(256), lds, s, F);      \
       return hipGetLastError();                                                             \
     }                                                                                       \
   }
@@ -1346,9 +1465,10 @@ hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 gri
 #undef X
   return hipErrorInvalidValue;
 }
-#define H2S_TILE_EXTERN(D, L) \
-  extern template hipError_t launch_tile<D, L>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
-#define H2S_TILE_INSTANCE(D, L) \
-  template hipError_t launch_tile<D, L>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+// (S: the SEMI instances, each chain's and stage's in a translation unit of their own)
+#define H2S_TILE_EXTERN(D, L, S) \
+  extern template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+#define H2S_TILE_INSTANCE(D, L, S) \
+  template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 
 }  // namespace h2s

@@ -33,6 +33,7 @@ class Tonemapper:
         self.device = device
         self.params: 'TonemapParams | None' = None
         self.lut_size = 0
+        self._layouts = ('planar', 'planar')   # what the context last got (h2s_set_frame_layout)
         if params is not None:
             self.set_params(params)
         if lut is not None:
@@ -93,6 +94,23 @@ class Tonemapper:
         return params
 
     # ---- execution ----------------------------------------------------------
+    def set_frame_layout(self, in_layout: str = 'planar', out_layout: str = 'planar') -> None:
+        """How later calls read their source batch and write their
+        destination batch ('planar' | 'semi'; h2s_set_frame_layout).  process,
+        query_path, debug_float and peak_stats set it from their batches'
+        ``layout``, so callers of those never need to."""
+        for name in (in_layout, out_layout):
+            if name not in _abi.LAYOUTS:
+                raise ValueError(f"layout must be 'planar' or 'semi', got {name!r}")
+        if (in_layout, out_layout) != self._layouts:
+            self._check(self._L.h2s_set_frame_layout(self._ctx, _abi.LAYOUTS[in_layout], _abi.LAYOUTS[out_layout]))
+            self._layouts = (in_layout, out_layout)
+
+    def _use_layouts(self, src: FrameBatch, dst: 'FrameBatch | None' = None) -> None:
+        # (a call without a destination batch leaves the output side as it is)
+        self.set_frame_layout(getattr(src, 'layout', 'planar'),
+                              self._layouts[1] if dst is None else getattr(dst, 'layout', 'planar'))
+
     @staticmethod
     def _stream_ptr(stream: Any) -> 'int | None':
         if stream is None:
@@ -111,18 +129,19 @@ class Tonemapper:
         n = src.nframes if nframes is None else nframes
         if n > src.nframes or n > dst.nframes:
             raise ValueError(f'nframes {n} exceeds the batch ({src.nframes} in, {dst.nframes} out)')
+        self._use_layouts(src, dst)
         di, do = src.descriptor(), dst.descriptor()
         self._check(self._L.h2s_process(self._ctx, ctypes.byref(di), ctypes.byref(do), int(n),
                                         self._stream_ptr(stream)))
 
-    def __call__(self, src: FrameBatch, stream: Any = None) -> FrameBatch:
+    def __call__(self, src: FrameBatch, stream: Any = None, out_layout: str = 'planar') -> FrameBatch:
         if self.params is None:
             raise ValueError('set_params first')
         if src.is_torch:
             dst = FrameBatch.empty_torch(src.nframes, src.width, src.height, self.params.bits_out,
-                                         src.buf.device)
+                                         src.buf.device, out_layout)
         else:
-            dst = FrameBatch.empty_numpy(src.nframes, src.width, src.height, self.params.bits_out)
+            dst = FrameBatch.empty_numpy(src.nframes, src.width, src.height, self.params.bits_out, out_layout)
         self.process(src, dst, stream)
         return dst
 
@@ -132,6 +151,7 @@ class Tonemapper:
 
     def query_path(self, src: FrameBatch, dst: FrameBatch) -> int:
         """The kernel path (_abi.PATH_*) h2s_process would take for src -> dst."""
+        self._use_layouts(src, dst)
         di, do = src.descriptor(), dst.descriptor()
         rc = self._L.h2s_query_path(self._ctx, ctypes.byref(di), ctypes.byref(do))
         if rc < 0:
@@ -144,6 +164,7 @@ class Tonemapper:
         the kernel h2s_process would use (the tile kernel's debug instance on
         the tile path)."""
         out = np.empty((3, src.height, src.width), dtype=np.float32)
+        self._use_layouts(src)
         d = src.descriptor()
         self._check(self._L.h2s_debug_float(self._ctx, ctypes.byref(d), int(stage), out.ctypes.data,
                                             _abi.LOC_HOST, self._stream_ptr(None)))
@@ -159,6 +180,7 @@ class Tonemapper:
         statistics process() folds into the smoothing (h2s_peak_stats)."""
         n = src.nframes
         fmax, favg = np.zeros(n), np.zeros(n)
+        self._use_layouts(src)
         di = src.descriptor()
         self._check(self._L.h2s_peak_stats(self._ctx, ctypes.byref(di), n, fmax.ctypes.data, favg.ctypes.data,
                                            self._stream_ptr(stream)))

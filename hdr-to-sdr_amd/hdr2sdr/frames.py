@@ -1,4 +1,5 @@
-"""Planar 4:2:0 frame batches (yuv420p / yuv420p10le / yuv420p12le).
+"""4:2:0 frame batches: planar (yuv420p / yuv420p10le / yuv420p12le) and
+semi-planar (nv12 / p010le / p012le).
 
 The reference never holds frames itself: ffmpeg owns every buffer
 (SURVEY.md §8b "Ownership").  Here the caller owns them, in device memory
@@ -11,6 +12,13 @@ frame = Y plane (H x W) then U (H/2 x W/2) then V, rows packed (linesize =
 width * bytes-per-sample).  A 3840x2160 10-bit frame is 24,883,200 B, so a
 288 GB MI355X holds >10,000 such frames; batches of 16-64 frames per launch
 keep the grid far above the 256-CU fill point.
+
+Semi-planar batches (``layout='semi'``: what hardware decoders produce and
+hardware encoders take) hold, per frame, the Y plane then one plane of
+interleaved (Cb, Cr) pairs (H/2 rows of W samples), the same number of bytes;
+10/12-bit samples carry the value in the high bits of their 16-bit word.  The
+kernels read and write both layouts in place (h2s_set_frame_layout);
+``to_layout`` is the host-side repack for tests and callers.
 """
 from __future__ import annotations
 
@@ -21,6 +29,9 @@ from typing import Any
 import numpy as np
 
 from . import _abi
+
+
+LAYOUTS = ('planar', 'semi')
 
 
 def sample_bytes(bits: int) -> int:
@@ -42,6 +53,11 @@ class FrameBatch:
     width: int
     height: int
     bits: int
+    layout: str = 'planar'
+
+    def __post_init__(self):
+        if self.layout not in LAYOUTS:
+            raise ValueError(f"layout must be 'planar' or 'semi', got {self.layout!r}")
 
     # ---- constructors ---------------------------------------------------
     @staticmethod
@@ -53,19 +69,22 @@ class FrameBatch:
         return nframes, width * height * 3 // 2
 
     @classmethod
-    def empty_torch(cls, nframes: int, width: int, height: int, bits: int, device: Any) -> 'FrameBatch':
+    def empty_torch(cls, nframes: int, width: int, height: int, bits: int, device: Any,
+                    layout: str = 'planar') -> 'FrameBatch':
         import torch
         dt = torch.uint8 if bits == 8 else torch.int16
         return cls(torch.empty(cls._shape(nframes, width, height, bits), dtype=dt, device=device),
-                   width, height, bits)
+                   width, height, bits, layout)
 
     @classmethod
-    def empty_numpy(cls, nframes: int, width: int, height: int, bits: int) -> 'FrameBatch':
+    def empty_numpy(cls, nframes: int, width: int, height: int, bits: int,
+                    layout: str = 'planar') -> 'FrameBatch':
         dt = np.uint8 if bits == 8 else np.uint16
-        return cls(np.zeros(cls._shape(nframes, width, height, bits), dtype=dt), width, height, bits)
+        return cls(np.zeros(cls._shape(nframes, width, height, bits), dtype=dt), width, height, bits, layout)
 
     @classmethod
-    def empty_pinned(cls, nframes: int, width: int, height: int, bits: int) -> 'FrameBatch':
+    def empty_pinned(cls, nframes: int, width: int, height: int, bits: int,
+                     layout: str = 'planar') -> 'FrameBatch':
         """Host batch in page-locked memory (DMA-able without a bounce copy:
         the host-buffer path of h2s_process then runs at PCIe speed). Falls
         back to pageable numpy memory when no GPU runtime is present."""
@@ -75,12 +94,12 @@ class FrameBatch:
                 dt = torch.uint8 if bits == 8 else torch.int16
                 t = torch.empty(cls._shape(nframes, width, height, bits), dtype=dt, pin_memory=True)
                 a = t.numpy() if bits == 8 else t.numpy().view(np.uint16)
-                fb = cls(a, width, height, bits)
+                fb = cls(a, width, height, bits, layout)
                 fb._pin = t          # keep the pinned allocation alive
                 return fb
         except (ImportError, RuntimeError):
             pass
-        return cls.empty_numpy(nframes, width, height, bits)
+        return cls.empty_numpy(nframes, width, height, bits, layout)
 
     @classmethod
     def from_planes(cls, y: np.ndarray, u: np.ndarray, v: np.ndarray, bits: int) -> 'FrameBatch':
@@ -107,8 +126,19 @@ class FrameBatch:
         csz = ysz // 4
         if p == 0:
             return self.buf[:, :ysz].reshape(self.nframes, h, w)
+        if self.layout == 'semi':
+            return self.uv[..., p - 1]
         off = ysz + (p - 1) * csz
         return self.buf[:, off:off + csz].reshape(self.nframes, h // 2, w // 2)
+
+    @property
+    def uv(self):
+        """The interleaved plane of a semi-planar batch as [F, H/2, W/2, 2]
+        ((Cb, Cr) last); ``u`` / ``v`` of such a batch are strided views of it."""
+        if self.layout != 'semi':
+            raise ValueError('uv is the interleaved plane of a semi-planar batch')
+        w, h = self.width, self.height
+        return self.buf[:, w * h:].reshape(self.nframes, h // 2, w // 2, 2)
 
     @property
     def y(self):
@@ -128,17 +158,60 @@ class FrameBatch:
         a = self.buf.detach().cpu().numpy()
         if self.bits != 8:
             a = a.view(np.uint16)
-        return FrameBatch(a, self.width, self.height, self.bits)
+        return FrameBatch(a, self.width, self.height, self.bits, self.layout)
 
     def to_torch(self, device: Any) -> 'FrameBatch':
         import torch
         if self.is_torch:
-            return FrameBatch(self.buf.to(device), self.width, self.height, self.bits)
+            return FrameBatch(self.buf.to(device), self.width, self.height, self.bits, self.layout)
         a = self.buf if self.bits == 8 else self.buf.view(np.int16)
-        return FrameBatch(torch.from_numpy(np.ascontiguousarray(a)).to(device), self.width, self.height, self.bits)
+        return FrameBatch(torch.from_numpy(np.ascontiguousarray(a)).to(device), self.width, self.height, self.bits,
+                          self.layout)
 
     def slice(self, start: int, stop: int) -> 'FrameBatch':
-        return FrameBatch(self.buf[start:stop], self.width, self.height, self.bits)
+        return FrameBatch(self.buf[start:stop], self.width, self.height, self.bits, self.layout)
+
+    def to_layout(self, layout: str) -> 'FrameBatch':
+        """A copy of the batch in ``layout`` (the batch itself when it already
+        is): planes interleaved or split, 10/12-bit codes moved to the high
+        bits of their words (semi) or back to the low bits (planar; whatever
+        the low bits of a semi word held is dropped).  A host / torch repack
+        for tests and callers: the product path reads and writes both layouts
+        in place and never calls it."""
+        if layout not in LAYOUTS:
+            raise ValueError(f"layout must be 'planar' or 'semi', got {layout!r}")
+        if layout == self.layout:
+            return self
+        sh = 0 if self.bits == 8 else 16 - self.bits
+        if self.is_torch:
+            import torch
+            dst = FrameBatch(torch.empty_like(self.buf), self.width, self.height, self.bits, layout)
+            # (int16 storage: the codes move as unsigned 16-bit words)
+            def up(x):
+                if not sh:
+                    return x
+                v = (x.to(torch.int32) << sh) & 0xFFFF
+                return (v - ((v & 0x8000) << 1)).to(torch.int16)   # the word's bits as int16
+
+            def down(x):
+                return ((x.to(torch.int32) & 0xFFFF) >> sh).to(torch.int16) if sh else x
+        else:
+            dst = FrameBatch(np.empty_like(self.buf), self.width, self.height, self.bits, layout)
+
+            def up(x):
+                return (x.astype(np.uint32) << sh).astype(self.buf.dtype) if sh else x
+
+            def down(x):
+                return x >> sh if sh else x
+        conv = up if layout == 'semi' else down
+        dst.y[...] = conv(self.y)
+        if layout == 'semi':
+            dst.uv[..., 0] = conv(self.u)
+            dst.uv[..., 1] = conv(self.v)
+        else:
+            dst.u[...] = conv(self.u)
+            dst.v[...] = conv(self.v)
+        return dst
 
     # ---- C-ABI descriptor ---------------------------------------------------
     def descriptor(self) -> _abi.H2SFrames:
@@ -160,11 +233,16 @@ class FrameBatch:
         fpitch = ysz + 2 * csz
         d.data[0] = base
         d.data[1] = base + ysz
-        d.data[2] = base + ysz + csz
         d.linesize[0] = w * sb
-        d.linesize[1] = d.linesize[2] = (w // 2) * sb
-        for p in range(3):
-            d.frame_pitch[p] = fpitch
+        if self.layout == 'semi':
+            # plane 1: the interleaved plane, a row of W samples; plane 2 unused (zero)
+            d.linesize[1] = w * sb
+            d.frame_pitch[0] = d.frame_pitch[1] = fpitch
+        else:
+            d.data[2] = base + ysz + csz
+            d.linesize[1] = d.linesize[2] = (w // 2) * sb
+            for p in range(3):
+                d.frame_pitch[p] = fpitch
         d.width, d.height, d.bits, d.location = w, h, self.bits, loc
         return d
 

@@ -9,6 +9,8 @@ ffmpeg has no external-filter ABI, so here ffmpeg keeps demux, decode,
 encode and mux. The tone-map chain moves onto the GPU between two pipes:
 
     decode:  ffmpeg -i IN -map 0:v:0 -f rawvideo -pix_fmt yuv420p1Xle -
+             (or p010le / p012le, and nv12 / p010le / p012le on the encode
+             pipe: the semi-planar layouts, ``in_layout`` / ``out_layout``)
     libh2s:  h2s_process() on batches of frames
     encode:  ffmpeg -f rawvideo … -i - -i IN <every non-filter option build() chose>
 
@@ -34,6 +36,8 @@ from .chain import DOVI_P5_ERROR, TonemapParams, is_dovi_profile5, parse_filter_
 
 # planar 4:2:0 formats the pipe carries, by bit depth
 PIPE_PIX_FMT = {8: 'yuv420p', 10: 'yuv420p10le', 12: 'yuv420p12le'}
+# the semi-planar formats (hardware decoder / encoder surfaces), by bit depth
+PIPE_PIX_FMT_SEMI = {8: 'nv12', 10: 'p010le', 12: 'p012le'}
 # encoder -pix_fmt values build() emits (src/ffmpeg_command.py:355-368) -> bits
 OUT_PIX_FMT_BITS = {'yuv420p': 8, 'yuv420p10le': 10, 'p010le': 10, 'yuv420p12le': 12}
 # setparams=color_primaries=bt709:color_trc=bt709:colorspace=bt709 (src/utils.py:40)
@@ -53,6 +57,10 @@ class PipePlan:
     input_path: str
     output_path: str
     reference_argv: 'list[str]' = field(default_factory=list)
+    # frame layouts on the two pipes ('planar' | 'semi'): what the decode side
+    # emits and what the encode side is fed
+    in_layout: str = 'planar'
+    layout: str = 'planar'
 
     @property
     def frame_bytes_in(self) -> int:
@@ -71,8 +79,16 @@ def _remap_input(spec: str) -> str:
 
 
 def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[str, Any] | None' = None,
-                   mode: str = 'compat8') -> PipePlan:
+                   mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar') -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
+
+    in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
+    the decode and encode pipes.  'semi' carries nv12 / p010le / p012le, which
+    libh2s reads and writes in place.  out_layout='auto' is semi exactly when
+    the reference's ``-pix_fmt`` is ``p010le`` (its hardware HEVC encoders,
+    src/ffmpeg_command.py:365-368): the encoder then takes the pipe's frames
+    as they are instead of repacking each one on the CPU.  in_layout='auto'
+    is planar (a software decoder's native output).
 
     properties: the reference's ``get_video_properties`` dict
     (src/utils.py:1040-1058): width, height, bit_depth, color_transfer.
@@ -138,13 +154,22 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     o_idx = len(out) - 2 if out and out[-1] == '-y' else len(out) - 1
     output_path = out[o_idx]
     encode_opts = out[:o_idx] + BT709_TAGS + out[o_idx:]
-    pipe_out = PIPE_PIX_FMT[bits_out]
+    for name in (in_layout, out_layout):
+        if name not in ('planar', 'semi', 'auto'):
+            raise ValueError(f"layout must be 'planar', 'semi' or 'auto', got {name!r}")
+    if in_layout == 'auto':
+        in_layout = 'planar'
+    if out_layout == 'auto':
+        out_layout = 'semi' if enc_pix_fmt == 'p010le' else 'planar'
+    pipe_in = (PIPE_PIX_FMT_SEMI if in_layout == 'semi' else PIPE_PIX_FMT)[bits_in]
+    pipe_out = (PIPE_PIX_FMT_SEMI if out_layout == 'semi' else PIPE_PIX_FMT)[bits_out]
     decode = [exe, '-loglevel', 'error', '-nostdin', '-i', input_path, '-map', '0:v:0',
-              '-f', 'rawvideo', '-pix_fmt', PIPE_PIX_FMT[bits_in], '-']
+              '-f', 'rawvideo', '-pix_fmt', pipe_in, '-']
     encode = [exe, '-loglevel', 'info', '-f', 'rawvideo', '-pix_fmt', pipe_out, '-s', f'{W}x{H}',
               '-r', fps, '-i', '-', '-i', input_path, '-map', '0:v:0'] + encode_opts
     return PipePlan(decode=decode, encode=encode, params=params, lut_path=lut_path, width=W, height=H,
-                    input_path=input_path, output_path=output_path, reference_argv=argv)
+                    input_path=input_path, output_path=output_path, reference_argv=argv,
+                    in_layout=in_layout, layout=out_layout)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -181,9 +206,9 @@ class H2SProcess:
         # page-locked staging: the pipe bytes go straight to / from HBM by DMA.
         # `depth` input slots let the decoder run ahead while the GPU stage
         # and the encoder work on earlier batches.
-        self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in)
+        self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout)
                      for _ in range(max(1, int(depth)))]
-        self._dst = FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_out)
+        self._dst = FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_out, plan.layout)
         self._free: 'queue.Queue[Optional[int]]' = queue.Queue()
         self._filled: 'queue.Queue[Optional[Tuple[int, int]]]' = queue.Queue()
         for i in range(len(self._src)):

@@ -58,7 +58,11 @@ extern "C" {
  *   4: H2S_OPT_LP_EXACT moves to key 5 and key 4 is reserved (H2S_E_INVALID_ARG:
  *      a 3.0 / 3.1 client that set key 4 as the old failure-injection hook
  *      fails loudly instead of switching kernels); the libplacebo branch's
- *      exact path computes stages 1-3 in double precision (see below). */
+ *      exact path computes stages 1-3 in double precision (see below).
+ * Added within 3.4, with no change of either number: h2s_set_frame_layout
+ * (semi-planar nv12 / p010le / p012le frame sets).  No struct, signature or
+ * default behaviour changes, so the symbol's presence in the loaded library
+ * is the feature test. */
 #define H2S_ABI_MINOR 4
 
 /* ---- error codes ------------------------------------------------------- */
@@ -112,6 +116,13 @@ enum h2s_desat_luma {
 
 /* Where a frame set lives. */
 enum h2s_location { H2S_LOC_DEVICE = 0, H2S_LOC_HOST = 1 };
+
+/* How a frame set's chroma is stored (h2s_set_frame_layout).  PLANAR: three
+ * planes, the code in the low bits (yuv420p / yuv420p10le / yuv420p12le).
+ * SEMI: the Y plane and one plane of interleaved (Cb, Cr) pairs, 16-bit
+ * samples with the code in the high bits (nv12 / p010le / p012le: what
+ * hardware decoders produce and hardware encoders take). */
+enum h2s_layout { H2S_LAYOUT_PLANAR = 0, H2S_LAYOUT_SEMI = 1 };
 
 /* Debug stages for h2s_debug_float: three float planes per pixel.
  * 1..4: R, G, B after the stage.  5: the quantiser's inputs, before rounding:
@@ -316,6 +327,21 @@ typedef struct h2s_frames {
   int32_t location; /* enum h2s_location   */
 } h2s_frames;
 
+/* The same record describes a semi-planar set (H2S_LAYOUT_SEMI) when the
+ * context's layout for that side says so:
+ *   plane 0: the Y plane, as above;
+ *   plane 1: the interleaved plane, width/2 (Cb, Cr) pairs per row and
+ *     height/2 rows, so linesize[1] >= width * bytes per sample;
+ *   plane 2: ignored (data NULL, linesize and frame_pitch 0 are fine).
+ * bits == 8 (nv12, output only): one byte per sample.  bits == 10 / 12
+ * (p010le / p012le; a decoder's "P016" too): little-endian 16-bit words with
+ * the value in the high bits: on input code = word >> (16 - bits), whatever
+ * the low bits hold (the h2s_lp_p010 TRUNCATE mask then applies to the code);
+ * on output word = code << (16 - bits), low bits zero.  Pitches may be
+ * padded as a decoder pads them; 16-bit planes need even linesize and
+ * frame_pitch.  Row starts that are 16-byte aligned (8 for nv12) run on the
+ * tile kernel, others on the generic one (h2s_query_path), as for planar. */
+
 typedef struct h2s_ctx h2s_ctx;
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -372,6 +398,17 @@ int h2s_debug_float(h2s_ctx *ctx, const h2s_frames *in, int stage,
  * options (negative H2S_E_* on invalid input). */
 int h2s_set_option(h2s_ctx *ctx, int key, int64_t value);
 int h2s_query_path(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out);
+
+/* ---- frame layout (enum h2s_layout; default PLANAR, PLANAR) ---------------
+ * How every later call on the context reads its `in` frames and writes its
+ * `out` frames: h2s_process and h2s_query_path (both), h2s_debug_float,
+ * h2s_peak_stats and h2s_preview_rgb24 / _batch (`in`; their float, RGB and
+ * statistics outputs are unaffected).  The two sides are independent.  The
+ * kernels read and write the surfaces in place: no repack pass, and output
+ * codes equal the planar ones sample for sample.  Only the arguments of later
+ * launches change, so the call does not wait for queued work.  An unknown
+ * value or a NULL ctx is H2S_E_INVALID_ARG. */
+int h2s_set_frame_layout(h2s_ctx *ctx, int in_layout, int out_layout);
 
 /* ---- dynamic peak (params.peak_detect, BT.2390 / spline) -----------------
  * h2s_peak_reset: forget the smoothing state (a new sequence / scene cut).
