@@ -1,5 +1,7 @@
 // h2s_api.hip — the C-ABI (include/h2s.h): contexts, parameter resolution,
-// LUT upload, frame validation, host staging and kernel timing.
+// LUT upload, frame validation, host staging and kernel timing.  Which kernels
+// a call launches is decided once (Route) and carried out by launch_route over
+// three primitives: launch_tiles, launch_columns and launch_two_pass.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -16,11 +18,11 @@
 #include "h2s_peak.h"
 
 namespace h2s {
-hipError_t launch_process(const KParams& P, bool vec, bool out8, hipStream_t s);
+enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2s_kernels.hip defines it
+hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s);
 hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s);
 bool fast_supported(int tonemap);
 hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg = 0);
-hipError_t launch_process_c444(const KParams& P, bool out8, hipStream_t s);
 hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float* wy8, bool out8, hipStream_t s);
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st);
 hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
@@ -603,9 +605,10 @@ void build_hlg_table(std::vector<float4>* out) {
 
 bool aligned(const void* p, long long a) { return ((uintptr_t)p % (uintptr_t)a) == 0; }
 
-// semi (here and below): the set is semi-planar (H2S_LAYOUT_SEMI): plane 1
-// holds (Cb, Cr) pairs, a row of it is as long as a luma row, plane 2 is unused
-int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi = 0) {
+// semi (here and below): the set's layout (enum h2s_layout, never defaulted);
+// semi-planar (H2S_LAYOUT_SEMI): plane 1 holds (Cb, Cr) pairs, a row of it is
+// as long as a luma row, plane 2 is unused
+int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi) {
   if (!f) return fail(c, H2S_E_INVALID_ARG, std::string(which) + " frames is NULL");
   if (f->width <= 0 || f->height <= 0) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": empty frame");
   if ((f->width & 1) || (f->height & 1))
@@ -632,7 +635,7 @@ int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, i
 
 // vector path needs 16-B luma / 8-B chroma alignment of every row start
 // (semi-planar: four pairs of the interleaved plane are one luma-sized access)
-bool vec_ok(const h2s_frames* f, bool out8, int semi = 0) {
+bool vec_ok(const h2s_frames* f, bool out8, int semi) {
   const long long ay = out8 ? 8 : 16, ac = semi ? ay : (out8 ? 4 : 8);
   const long long a[3] = {ay, ac, ac};
   for (int p = 0; p < (semi ? 2 : 3); p++)
@@ -643,13 +646,13 @@ bool vec_ok(const h2s_frames* f, bool out8, int semi = 0) {
 // tile kernel: at least one 64-pixel tile, every row start 16-B aligned (8-B
 // for 8-bit chroma output)
 // (semi-planar: the same for the two planes it has)
-bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, int in_semi = 0, int out_semi = 0) {
-  if (in->width < tw) return false;  // width % tw columns go to k_process (launch_chain)
+bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, int in_semi, int out_semi) {
+  if (in->width < tw) return false;  // width % tw columns go to k_process (launch_columns)
   for (int p = 0; p < 3; p++) {
     if (!(in_semi && p == 2) &&
         (!aligned(in->data[p], 16) || in->linesize[p] % 16 || in->frame_pitch[p] % 16))
       return false;
-    const long long a = out8 ? (p ? 8 : 8) : 16;
+    const long long a = out8 ? 8 : 16;
     if (!(out_semi && p == 2) &&
         (!aligned(out->data[p], a) || out->linesize[p] % a || out->frame_pitch[p] % a))
       return false;
@@ -665,7 +668,7 @@ size_t frame_bytes(const h2s_frames* f) {
 // tight device copy descriptor laid out in `base`
 // (semi-planar: the interleaved plane takes the two chroma planes' place,
 // so a frame's bytes are the same)
-h2s_frames tight(const h2s_frames* f, void* base, int semi = 0) {
+h2s_frames tight(const h2s_frames* f, void* base, int semi) {
   h2s_frames t = *f;
   const long long bps = f->bits == 8 ? 1 : 2;
   const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4;
@@ -681,8 +684,13 @@ h2s_frames tight(const h2s_frames* f, void* base, int semi = 0) {
   return t;
 }
 
+// the set the kernels bind: a device set itself, a host set's tight copy staged in `base`
+h2s_frames device_view(const h2s_frames* f, void* base, int semi) {
+  return f->location == H2S_LOC_HOST ? tight(f, base, semi) : *f;
+}
+
 // the whole batch is one contiguous span laid out as tight() describes
-bool is_tight(const h2s_frames* f, int semi = 0) {
+bool is_tight(const h2s_frames* f, int semi) {
   const long long bps = f->bits == 8 ? 1 : 2;
   const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4, fb = ysz + 2 * csz;
   if (semi)
@@ -694,7 +702,7 @@ bool is_tight(const h2s_frames* f, int semi = 0) {
          (const uint8_t*)f->data[2] == (const uint8_t*)f->data[1] + csz;
 }
 
-hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi = 0) {
+hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi) {
   const long long bps = src->bits == 8 ? 1 : 2;
   if (is_tight(src, semi) && is_tight(dst, semi))  // one DMA for the whole batch
     return hipMemcpyAsync(dst->data[0], src->data[0], (size_t)src->frame_pitch[0] * nframes, hipMemcpyDefault, s);
@@ -1135,17 +1143,6 @@ static int prepare(h2s_ctx* c, KParams* k, bool need_lut = true) {
   return 0;
 }
 
-// the generic kernel over the columns right of the last whole 64-pixel tile
-// (left-sited chroma needs no left neighbour, so the seam is exact)
-static hipError_t launch_tail(const KParams& k, int nframes, bool vec, bool out8, hipStream_t s, int tw) {
-  const int w64 = k.W & ~(tw - 1);
-  KParams kt = k;
-  kt.gx0 = w64 / 8;
-  kt.ngx = (k.cw - w64 / 2 + 3) / 4;
-  kt.total = (long long)nframes * k.ch * kt.ngx;
-  return h2s::launch_process(kt, vec, out8, s);
-}
-
 // BICUBIC chroma taps (oracle_chroma_taps): horizontal 7 taps around the
 // left-sited position, vertical 8 around the centre-sited one, normalised
 static void chroma_taps(float* wx7, float* wy8) {
@@ -1163,84 +1160,57 @@ static void chroma_taps(float* wx7, float* wy8) {
   for (int j = 0; j < 8; j++) wy8[j] = (float)(ty[j] / sy);
 }
 
-// BICUBIC chroma: frame by frame, per-pixel chroma into the context scratch
-// then the decimation (h2s_kernels.hip launch_two_pass)
-static hipError_t launch_two_pass_frames(const h2s_ctx* c, const KParams& k, bool out8, int nframes, hipStream_t s) {
-  float wx[7], wy[8];
-  chroma_taps(wx, wy);
-  for (int f = 0; f < nframes; f++) {
-    KParams kf = k;
-    for (int p = 0; p < 3; p++) {
-      kf.in[p] += f * kf.in_fp[p];
-      kf.out[p] += f * kf.out_fp[p];
-    }
-    kf.nframes = 1;
-    kf.total = (long long)kf.ch * kf.ngx;
-    kf.chr444 = c->d_chr;
-    hipError_t e = h2s::launch_process_c444(kf, out8, s);
-    if (e == hipSuccess) e = h2s::launch_chroma_bicubic(kf, wx, wy, out8, s);
-    if (e != hipSuccess) return e;
+// How one call launches, decided once per call (process_frames,
+// h2s_debug_float): the kernels (choose_path), what the rows' alignment and
+// the output depth allow, the two sets' layouts and the stream.  A caller that
+// spreads the call over its own streams copies it with another stream (on)
+struct Route {
+  int path;                    // H2S_PATH_*
+  bool vec, out8;
+  int in_layout, out_layout;   // enum h2s_layout
+  hipStream_t s;
+  bool tile() const { return path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL; }
+  Route on(hipStream_t other) const {
+    Route r = *this;
+    r.s = other;
+    return r;
   }
-  return hipSuccess;
+};
+
+// k restricted to frames [f0, f0 + n)
+static KParams frame_range(const KParams& k, int f0, int n) {
+  KParams kf = k;
+  for (int p = 0; p < 3; p++) {
+    kf.in[p] += (long long)f0 * kf.in_fp[p];
+    kf.out[p] += (long long)f0 * kf.out_fp[p];
+  }
+  kf.nframes = n;
+  kf.total = (long long)n * kf.ch * kf.ngx;
+  return kf;
 }
 
-static hipError_t launch_chain(const h2s_ctx* c, const KParams& k, bool fast, bool vec, bool out8, int nframes,
-                               hipStream_t s, const h2s::CurveConsts* cvf, bool tail, int dbg, float* dbg_out,
-                               float2* chr444);
+// the width the tile kernel covers: the whole 64-pixel tiles
+static int tiled_width(const KParams& k) { return k.W & ~(h2s::TBW - 1); }
 
-// BICUBIC chroma with the tile kernel, frame by frame: k_tile writes luma
-// and every pixel's (Cb, Cr) into the context scratch (the generic C444
-// kernel covers the width % 64 columns), then the decimation pass
-static hipError_t launch_tile_two_pass(const h2s_ctx* c, const KParams& k, bool out8, int nframes, hipStream_t s) {
-  float wx[7], wy[8];
-  chroma_taps(wx, wy);
-  for (int f = 0; f < nframes; f++) {
-    KParams kf = k;
-    for (int p = 0; p < 3; p++) {
-      kf.in[p] += f * kf.in_fp[p];
-      kf.out[p] += f * kf.out_fp[p];
-    }
-    kf.nframes = 1;
-    kf.total = (long long)kf.ch * kf.ngx;
-    kf.chr444 = c->d_chr;
-    hipError_t e = launch_chain(c, kf, true, false, out8, 1, s, nullptr, false, 0, nullptr, c->d_chr);
-    const int w64 = k.W & ~(h2s::TBW - 1);
-    if (e == hipSuccess && w64 != k.W) {
-      KParams kt = kf;
-      kt.gx0 = w64 / 8;
-      kt.ngx = (k.cw - w64 / 2 + 3) / 4;
-      kt.total = (long long)k.ch * kt.ngx;
-      e = h2s::launch_process_c444(kt, out8, s);
-    }
-    if (e == hipSuccess) e = h2s::launch_chroma_bicubic(kf, wx, wy, out8, s);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+// what a tile launch does beside the plain conversion
+struct TileOpts {
+  const h2s::CurveConsts* cv_frames = nullptr;   // dynamic peak: one curve record per frame of the launch
+  int dbg = 0;                 // > 0: the debug instance for that stage, which writes
+  float* dbg_out = nullptr;    //      frame 0's float planes here
+  float2* chr444 = nullptr;    // BICUBIC pass 1: every pixel's (Cb, Cr) here, no chroma planes
+};
 
-// one launch of the chain over nframes frames described by k.  cvf: per-frame
-// curve records (dynamic peak, fast kernel); tail = false leaves the ragged
-// right columns to the caller; dbg > 0: the tile kernel's debug instance for
-// that stage, writing frame 0's planes to dbg_out
-static hipError_t launch_chain(const h2s_ctx* c, const KParams& k, bool fast, bool vec, bool out8, int nframes,
-                               hipStream_t s, const h2s::CurveConsts* cvf = nullptr, bool tail = true, int dbg = 0,
-                               float* dbg_out = nullptr, float2* chr444 = nullptr) {
-  if (!fast) {
-    if (c->params.chroma_filter == H2S_CHROMA_BICUBIC) return launch_two_pass_frames(c, k, out8, nframes, s);
-    return h2s::launch_process(k, vec, out8, s);
-  }
-  if (c->params.chroma_filter == H2S_CHROMA_BICUBIC && !dbg && !chr444) return launch_tile_two_pass(c, k, out8, nframes, s);
+// the tile kernel over the whole 64-pixel tiles of k's frames
+static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& r, const TileOpts& o = {}) {
   FastParams F;
   resolve_fast(c, k, &F);
   for (int p = 0; p < 3; p++) {
     F.in[p] = k.in[p], F.in_ls[p] = k.in_ls[p], F.in_fp[p] = k.in_fp[p];
     F.out[p] = k.out[p], F.out_ls[p] = k.out_ls[p], F.out_fp[p] = k.out_fp[p];
   }
-  // k_tile covers the whole 64-pixel tiles; the chroma right halo of its last
-  // tile reads the real column (F.cw stays the frame's), so the split is exact
-  const int tw = h2s::TBW;
-  const int w64 = k.W & ~(tw - 1);
-  F.W = w64, F.H = k.H, F.cw = k.cw, F.ch = k.ch;
+  // the chroma right halo of the last tile reads the real column (F.cw stays
+  // the frame's), so the split from the ragged columns is exact
+  F.W = tiled_width(k), F.H = k.H, F.cw = k.cw, F.ch = k.ch;
   F.chroma_edge = k.chroma_edge;
   F.in_semi = k.in_cstep == 2, F.in_sh = k.in_sh, F.out_semi = k.out_cstep == 2, F.out_sh = k.out_sh;
   for (int p = 0; p < 3; p++) {
@@ -1248,22 +1218,67 @@ static hipError_t launch_chain(const h2s_ctx* c, const KParams& k, bool fast, bo
     F.in_bytes[p] = (int)(ib < 0x7fffffff ? ib : 0x7fffffff);
     F.out_bytes[p] = (int)(ob < 0x7fffffff ? ob : 0x7fffffff);
   }
-  F.nbx = (unsigned)(w64 / tw);
+  F.nbx = (unsigned)(F.W / h2s::TBW);
   F.nby = (unsigned)((k.H + h2s::TBH - 1) / h2s::TBH);
-  F.nframes = (unsigned)nframes;
+  F.nframes = (unsigned)k.nframes;
   F.tpb = c->tiles_per_block;
-  F.cv_frames = cvf;
-  F.dbg = dbg_out;
+  F.cv_frames = o.cv_frames;
+  F.dbg = o.dbg_out;
   F.dbg_w = k.W;
   F.dbg_lut = c->d_lut;
   F.inv_nm1 = 1.0f / (float)(c->lut_n - 1);
-  F.chr444 = chr444;
+  F.chr444 = o.chr444;
   F.chr_w = k.W;
   F.inv_c56 = 1.0f / F.c56;
   const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
-  hipError_t e = h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, s, dbg);
-  if (e != hipSuccess || w64 == k.W || !tail || dbg) return e;
-  return launch_tail(k, nframes, vec, out8, s, tw);
+  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, o.dbg);
+}
+
+// the generic kernel over a column range of k's frames: every column, or the
+// ragged ones right of the last whole tile (left-sited chroma needs no left
+// neighbour, so the seam is exact; none: no launch).  k.chr444 set: BICUBIC
+// pass 1 (luma, and every pixel's chroma into k.chr444)
+enum Columns { COLUMNS_ALL, COLUMNS_RAGGED };
+
+static hipError_t launch_columns(const KParams& k, const Route& r, Columns cols) {
+  KParams kc = k;
+  if (cols == COLUMNS_RAGGED) {
+    const int w64 = tiled_width(k);
+    kc.gx0 = w64 / 8;
+    kc.ngx = (k.cw - w64 / 2 + 3) / 4;
+    kc.total = (long long)k.nframes * k.ch * kc.ngx;
+  }
+  const unsigned form = (r.vec ? h2s::PF_VEC : 0) | (r.out8 ? h2s::PF_OUT8 : 0) | (k.chr444 ? h2s::PF_C444 : 0);
+  return h2s::launch_process(kc, form, r.s);
+}
+
+// BICUBIC chroma, frame by frame: pass 1 writes luma and every pixel's
+// (Cb, Cr) into the context scratch (the tile kernel, with the generic kernel
+// over the ragged columns, or the generic kernel over every column), then the
+// decimation pass writes the chroma planes
+static hipError_t launch_two_pass(const h2s_ctx* c, const KParams& k, const Route& r) {
+  float wx[7], wy[8];
+  chroma_taps(wx, wy);
+  TileOpts pass1;
+  pass1.chr444 = c->d_chr;
+  for (int f = 0; f < k.nframes; f++) {
+    KParams kf = frame_range(k, f, 1);
+    kf.chr444 = c->d_chr;
+    hipError_t e = r.tile() ? launch_tiles(c, kf, r, pass1) : hipSuccess;
+    if (e == hipSuccess) e = launch_columns(kf, r, r.tile() ? COLUMNS_RAGGED : COLUMNS_ALL);
+    if (e == hipSuccess) e = h2s::launch_chroma_bicubic(kf, wx, wy, r.out8, r.s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// one conversion of k's frames as the route says (static peak; the dynamic
+// peak's launches are run_dynamic_peak's)
+static hipError_t launch_route(const h2s_ctx* c, const KParams& k, const Route& r) {
+  if (c->params.chroma_filter == H2S_CHROMA_BICUBIC) return launch_two_pass(c, k, r);
+  if (!r.tile()) return launch_columns(k, r, COLUMNS_ALL);
+  const hipError_t e = launch_tiles(c, k, r);
+  return e == hipSuccess ? launch_columns(k, r, COLUMNS_RAGGED) : e;
 }
 
 // the tile kernel serves: both of the reference's chains (the CPU chain, and
@@ -1349,9 +1364,10 @@ static int peak_done(h2s_ctx* c, hipStream_t s) { return c->peak_use.mark(c, s, 
 // for stats_nf frames: partial records | histograms | the finish counter; the
 // histograms and the counter are zero between launches (cleared at
 // allocation, left zero by the kernels)
-static int frame_stats(h2s_ctx* c, const KParams& k, int nframes, hipStream_t s, h2s::PeakState* st,
-                       h2s::CurveConsts* out, int f0 = 0) {
+static int frame_stats(h2s_ctx* c, const KParams& k, hipStream_t s, h2s::PeakState* st, h2s::CurveConsts* out,
+                       int f0 = 0) {
   const h2s::PeakModel m = peak_model(c, k);
+  const int nframes = k.nframes;
   if (nframes > c->stats_nf) {
     const size_t nf = (size_t)nframes;
     const size_t part = nf * h2s::PEAK_BLOCKS_MAX * sizeof(float2), zero = (nf * h2s::PEAK_BINS + 1) * sizeof(unsigned);
@@ -1377,18 +1393,6 @@ static int frame_stats(h2s_ctx* c, const KParams& k, int nframes, hipStream_t s,
   return e == hipSuccess ? 0 : hip_fail(c, e, "peak statistics");
 }
 
-// k restricted to frames [f0, f0 + n)
-static KParams frame_range(const KParams& k, int f0, int n) {
-  KParams kf = k;
-  for (int p = 0; p < 3; p++) {
-    kf.in[p] += (long long)f0 * kf.in_fp[p];
-    kf.out[p] += (long long)f0 * kf.out_fp[p];
-  }
-  kf.nframes = n;
-  kf.total = (long long)n * kf.ch * kf.ngx;
-  return kf;
-}
-
 static int peak_streams(h2s_ctx* c, int nev) {
   for (Stream& ps : c->pk_s)
     if (int rc = ps.get(c, "peak stream")) return rc;
@@ -1403,8 +1407,9 @@ static int peak_streams(h2s_ctx* c, int nev) {
 // chunks convert on alternating streams, so that neither a chunk boundary
 // nor the statistics leave the chip idle.  The state still advances frame by
 // frame in order (the statistics stream is serial), exactly as one launch.
-static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool out8, int nframes, hipStream_t s) {
-  const int C = c->peak_chunk, nch = (nframes + C - 1) / C;
+static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, const Route& r) {
+  const int nframes = k.nframes, C = c->peak_chunk, nch = (nframes + C - 1) / C;
+  hipStream_t s = r.s;
   int rc;
   // every allocation before the first launch (hipFree of a grown buffer
   // would wait for the device)
@@ -1427,11 +1432,13 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
   for (int j = 0; j < nch; j++) {
     const int f0 = j * C, n = std::min(C, nframes - f0);
     const KParams kj = frame_range(k, f0, n);
-    if ((rc = frame_stats(c, kj, n, ss, c->d_pk, c->d_curve + f0, f0))) return fail_joined(rc);
+    if ((rc = frame_stats(c, kj, ss, c->d_pk, c->d_curve + f0, f0))) return fail_joined(rc);
     hipEvent_t ev = c->pk_ev[2 + j].ev;
     if ((e = hipEventRecord(ev, ss)) != hipSuccess || (e = hipStreamWaitEvent(st[j & 1], ev, 0)) != hipSuccess)
       return fail_joined(hip_fail(c, e, "peak schedule"));
-    if ((e = launch_chain(c, kj, true, vec, out8, n, st[j & 1], c->d_curve + f0, false)) != hipSuccess)
+    TileOpts curves;
+    curves.cv_frames = c->d_curve + f0;
+    if ((e = launch_tiles(c, kj, r.on(st[j & 1]), curves)) != hipSuccess)
       return fail_joined(hip_fail(c, e, "kernel launch"));
   }
   // s joins the statistics stream (the state) and the second conversion stream
@@ -1446,23 +1453,25 @@ static int run_dynamic_peak_chunked(h2s_ctx* c, const KParams& k, bool vec, bool
 // in one launch (a record per frame, selected by the tile's frame index), so
 // the chip stays full; the generic kernel and the ragged tail columns go frame
 // by frame, each launch reading its frame's record.
-static int run_dynamic_peak(h2s_ctx* c, const KParams& k, bool fast, bool vec, bool out8, int nframes, hipStream_t s) {
+static int run_dynamic_peak(h2s_ctx* c, const KParams& k, const Route& r) {
+  const int nframes = k.nframes;
+  hipStream_t s = r.s;
   int rc;
   if ((rc = ensure_peak_state(c)) || (rc = peak_order(c, s))) return rc;
   if ((rc = c->d_curve.reserve(c, (size_t)nframes * sizeof(h2s::CurveConsts), "curve records"))) return rc;
-  if (fast && (k.W & (h2s::TBW - 1)) == 0 && c->peak_chunk > 0 && nframes > c->peak_chunk)
-    return run_dynamic_peak_chunked(c, k, vec, out8, nframes, s);
-  if ((rc = frame_stats(c, k, nframes, s, c->d_pk, c->d_curve))) return rc;
+  if (r.path == H2S_PATH_TILE && c->peak_chunk > 0 && nframes > c->peak_chunk) return run_dynamic_peak_chunked(c, k, r);
+  if ((rc = frame_stats(c, k, s, c->d_pk, c->d_curve))) return rc;
   hipError_t e;
-  if (fast) {
-    e = launch_chain(c, k, true, vec, out8, nframes, s, c->d_curve, false);
-    if (e != hipSuccess) return hip_fail(c, e, "kernel launch");
+  if (r.tile()) {
+    TileOpts curves;
+    curves.cv_frames = c->d_curve;
+    if ((e = launch_tiles(c, k, r, curves)) != hipSuccess) return hip_fail(c, e, "kernel launch");
   }
-  if (!fast || (k.W & (h2s::TBW - 1)) != 0) {
+  if (r.path != H2S_PATH_TILE) {
     for (int f = 0; f < nframes; f++) {
       KParams kf = frame_range(k, f, 1);
       kf.cv = c->d_curve + f;
-      e = fast ? launch_tail(kf, 1, vec, out8, s, h2s::TBW) : launch_chain(c, kf, false, vec, out8, 1, s);
+      e = r.tile() ? launch_columns(kf, r, COLUMNS_RAGGED) : launch_route(c, kf, r);
       if (e != hipSuccess) return hip_fail(c, e, "kernel launch");
     }
   }
@@ -1538,8 +1547,8 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   h2s_frames out = *in;                       // geometry only: the statistics read the input planes
-  fill_geometry(&k, in, &out, nframes, c->in_layout, 0);
-  if ((rc = peak_order(c, s)) || (rc = frame_stats(c, k, nframes, s, nullptr, nullptr))) return rc;
+  fill_geometry(&k, in, &out, nframes, c->in_layout, H2S_LAYOUT_PLANAR);
+  if ((rc = peak_order(c, s)) || (rc = frame_stats(c, k, s, nullptr, nullptr))) return rc;
   std::vector<double2> st(nframes);
   hipError_t e = hipMemcpyAsync(st.data(), c->d_fstat, nframes * sizeof(double2), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1577,10 +1586,11 @@ static void timing_end(h2s_ctx* c, hipStream_t s) {
 // Staging holds the whole batch (no buffer reuse, so no WAR hazards); all
 // three streams start after the work already queued on `s`, and `s` waits
 // for them before the call returns. din/dout: staged (or caller's device)
-// descriptors for frame 0.
+// descriptors for frame 0; k binds the whole batch (k.nframes frames of them).
 static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const h2s_frames* out,
-                             const h2s_frames& din, const h2s_frames& dout, int nframes, bool fast, bool vec,
-                             bool out8, hipStream_t s, bool dyn_peak) {
+                             const h2s_frames& din, const h2s_frames& dout, const Route& r, bool dyn_peak) {
+  const int nframes = k.nframes;
+  hipStream_t s = r.s;
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
   for (Stream& ps : c->ps)
     if (int rc = ps.get(c, "pipeline stream")) return rc;
@@ -1602,26 +1612,26 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     const h2s_frames ci = frames_at(&din, f0), co = frames_at(&dout, f0);
     if (host_in) {
       const h2s_frames hi = frames_at(in, f0);
-      if ((e = copy_frames(&ci, &hi, nf, s_in, c->in_layout)) != hipSuccess) what = "host->device copy";
+      if ((e = copy_frames(&ci, &hi, nf, s_in, r.in_layout)) != hipSuccess) what = "host->device copy";
       else if ((e = hipEventRecord(c->pev[i].ev, s_in)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       if (what) break;
     }
     if (i == 0) timing_begin(c, s_cmp);
-    fill_geometry(&k, &ci, &co, nf, c->in_layout, c->out_layout);
+    fill_geometry(&k, &ci, &co, nf, r.in_layout, r.out_layout);
     if (dyn_peak) {
-      if (int rc = run_dynamic_peak(c, k, fast, vec, out8, nf, s_cmp)) {
+      if (int rc = run_dynamic_peak(c, k, r.on(s_cmp))) {
         sync_all();
         return rc;
       }
-    } else if ((e = launch_chain(c, k, fast, vec, out8, nf, s_cmp)) != hipSuccess) {
+    } else if ((e = launch_route(c, k, r.on(s_cmp))) != hipSuccess) {
       what = "kernel launch";
     }
     if (!what && host_out) {
       const h2s_frames ho = frames_at(out, f0);
       if ((e = hipEventRecord(c->pev[kMaxChunks + i].ev, s_cmp)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_out, c->pev[kMaxChunks + i].ev, 0)) != hipSuccess) what = "pipeline ordering";
-      else if ((e = copy_frames(&ho, &co, nf, s_out, c->out_layout)) != hipSuccess) what = "device->host copy";
+      else if ((e = copy_frames(&ho, &co, nf, s_out, r.out_layout)) != hipSuccess) what = "device->host copy";
     }
   }
   if (what) {  // drain whatever was queued before returning the caller's buffers
@@ -1639,38 +1649,35 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
   return 0;
 }
 
-int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, void* hip_stream) {
-  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+// h2s_process for the two layouts given (the context's own for its callers'
+// sets; a preview's chain output is planar whatever the context's is).
+// Nothing it calls reads c->in_layout / c->out_layout
+static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
+                          int in_layout, int out_layout) {
   if (nframes < 0) return fail(c, H2S_E_INVALID_ARG, "nframes < 0");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  const int in_semi = c->in_layout, out_semi = c->out_layout;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_semi))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output", out_semi))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_layout))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", out_layout))) return rc;
   if (in->width != out->width || in->height != out->height)
     return fail(c, H2S_E_INVALID_ARG, "input and output frame sizes differ");
   if (nframes == 0) return 0;
   DeviceGuard g(c->device);
-  hipStream_t s = (hipStream_t)hip_stream;
   const bool out8 = c->params.bits_out == 8;
 
-  h2s_frames din = *in, dout = *out;
+  // host sets are staged: input, then (256-byte aligned) output
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
-  if (host_in || host_out) {
-    const size_t ib = host_in ? frame_bytes(in) * nframes : 0, ob = host_out ? frame_bytes(out) * nframes : 0;
-    const size_t need = ((ib + 255) / 256) * 256 + ob;
-    if ((rc = c->d_stage.reserve(c, need, "staging"))) return rc;
-    if (host_in) din = tight(in, c->d_stage, in_semi);
-    if (host_out) dout = tight(out, c->d_stage + ((ib + 255) / 256) * 256, out_semi);
-  }
-  fill_geometry(&k, &din, &dout, nframes, in_semi, out_semi);
-  const bool vec = vec_ok(&din, false, in_semi) && vec_ok(&dout, out8, out_semi);
+  const size_t ib = host_in ? (frame_bytes(in) * nframes + 255) / 256 * 256 : 0;
+  const size_t ob = host_out ? frame_bytes(out) * nframes : 0;
+  if ((host_in || host_out) && (rc = c->d_stage.reserve(c, ib + ob, "staging"))) return rc;
+  const h2s_frames din = device_view(in, c->d_stage, in_layout), dout = device_view(out, c->d_stage + ib, out_layout);
+  fill_geometry(&k, &din, &dout, nframes, in_layout, out_layout);
   // fast path: the tile kernel over whole 64 x 32 tiles; the generic kernel
   // covers the rest (choose_path / fast_params_ok) and the ragged columns
-  const int path = choose_path(c, k, &din, &dout, out8);
-  const bool fast = path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL;
-  if (fast && k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) return rc;
+  const Route r{choose_path(c, k, &din, &dout, out8), vec_ok(&din, false, in_layout) && vec_ok(&dout, out8, out_layout),
+                out8, in_layout, out_layout, s};
+  if (r.tile() && k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) return rc;
   // BICUBIC chroma (generic two-pass, or k_tile pass 1) uses the context scratch
   const bool two_pass = c->params.chroma_filter == H2S_CHROMA_BICUBIC;
   if (two_pass) {
@@ -1685,18 +1692,18 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   // statistics, IIR and curve records run on the device, stream-ordered per
   // chunk on the compute stream, so the state still advances frame by frame)
   if ((host_in || host_out) && nframes > 1 && !c->serial_host)
-    return process_pipelined(c, k, in, out, din, dout, nframes, fast, vec, out8, s, dyn_peak);
+    return process_pipelined(c, k, in, out, din, dout, r, dyn_peak);
   if (host_in) {
-    hipError_t e = copy_frames(&din, in, nframes, s, in_semi);
+    hipError_t e = copy_frames(&din, in, nframes, s, in_layout);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "host->device copy"));
   }
   timing_begin(c, s);
   hipError_t e;
   if (dyn_peak) {
-    if ((rc = run_dynamic_peak(c, k, fast, vec, out8, nframes, s))) return queued_exit(c, s, rc);
+    if ((rc = run_dynamic_peak(c, k, r))) return queued_exit(c, s, rc);
     e = hipSuccess;
   } else {
-    e = launch_chain(c, k, fast, vec, out8, nframes, s);
+    e = launch_route(c, k, r);
   }
   if (e == hipSuccess && c->fail_after_launch) {
     c->fail_after_launch = false;
@@ -1705,7 +1712,7 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
   if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "kernel launch"));
   timing_end(c, s);
   if (host_out) {
-    e = copy_frames(out, &dout, nframes, s, out_semi);
+    e = copy_frames(out, &dout, nframes, s, out_layout);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "device->host copy"));
   }
   if (two_pass && (rc = c->chr_use.mark(c, s, "two-pass event"))) return queued_exit(c, s, rc);
@@ -1715,6 +1722,11 @@ int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nfr
     return 0;
   }
   return note_launch(c, s);
+}
+
+int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, void* hip_stream) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  return process_frames(c, in, out, nframes, (hipStream_t)hip_stream, c->in_layout, c->out_layout);
 }
 
 int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb, int out_location,
@@ -1738,26 +1750,26 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   Dev<uint8_t> scratch;  // freed on every exit, after s has been waited for
   if ((rc = scratch.reserve(c, ib + fb + pb + 256, "debug"))) return rc;
   uint8_t* base = scratch;
-  h2s_frames din = *in;
+  const h2s_frames din = device_view(in, base, c->in_layout);
   hipError_t e;
-  if (in->location == H2S_LOC_HOST) {
-    din = tight(in, base, c->in_layout);
-    if ((e = copy_frames(&din, in, 1, s, c->in_layout)) != hipSuccess) return hip_fail(c, e, "debug copy");
-  }
-  fo = tight(&fo, base + ib);
+  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_layout)) != hipSuccess)
+    return hip_fail(c, e, "debug copy");
+  fo = tight(&fo, base + ib, H2S_LAYOUT_PLANAR);   // (the call's own planar scratch frame)
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
-  fill_geometry(&k, &din, &fo, 1, c->in_layout, 0);   // (fo: the call's own planar scratch frame)
+  fill_geometry(&k, &din, &fo, 1, c->in_layout, H2S_LAYOUT_PLANAR);
   const bool out8 = c->params.bits_out == 8;
-  const int path = choose_path(c, k, &din, &fo, out8);
+  const Route r{choose_path(c, k, &din, &fo, out8), false, out8, c->in_layout, H2S_LAYOUT_PLANAR, s};
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
   e = h2s::launch_debug(k, stage, dout, s);
-  if (e == hipSuccess && (path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL)) {
+  if (e == hipSuccess && r.tile()) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
       return rc;
     }
-    e = launch_chain(c, k, true, false, out8, 1, s, nullptr, false, stage, dout);
+    TileOpts debug;
+    debug.dbg = stage, debug.dbg_out = dout;
+    e = launch_tiles(c, k, r, debug);
   }
   if (e == hipSuccess && out_location == H2S_LOC_HOST) e = hipMemcpyAsync(out_rgb, dout, ob, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1820,10 +1832,8 @@ int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
   if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_layout))) return rc;
   // host sets are staged into tight device copies, whose alignment decides
-  h2s_frames din = *in, dout = *out;
   uint8_t* fake = (uint8_t*)(uintptr_t)4096;
-  if (in->location == H2S_LOC_HOST) din = tight(in, fake, c->in_layout);
-  if (out->location == H2S_LOC_HOST) dout = tight(out, fake, c->out_layout);
+  const h2s_frames din = device_view(in, fake, c->in_layout), dout = device_view(out, fake, c->out_layout);
   fill_geometry(&k, &din, &dout, 1, c->in_layout, c->out_layout);
   return choose_path(c, k, &din, &dout, c->params.bits_out == 8);
 }
@@ -1887,14 +1897,6 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
     return fail(c, H2S_E_INVALID_ARG, "preview needs params.bits_out == 8 (the chain's yuv420p)");
   int rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout);
   if (rc) return rc;
-  // the chain's output here is the call's own yuv420p scratch: planar, whatever
-  // layout the context writes its callers' frames in
-  struct PlanarOut {
-    h2s_ctx* c;
-    int saved;
-    explicit PlanarOut(h2s_ctx* c_) : c(c_), saved(c_->out_layout) { c->out_layout = H2S_LAYOUT_PLANAR; }
-    ~PlanarOut() { c->out_layout = saved; }
-  } planar_out(c);
   const int W = in->width, H = in->height;
   const bool scale = out_w != W || out_h != H;
   if (scale && (out_w > 4 * 8192 || out_h > 4 * 8192 || (double)W / out_w > 12.0 || (double)H / out_h > 12.0))
@@ -1950,9 +1952,11 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
   }
   if ((rc = c->d_prev.reserve(c, need, "preview scratch"))) return rc;
   uint8_t* base = c->d_prev;
+  // the chain's output here is the call's own yuv420p scratch: planar, whatever
+  // layout the context writes its callers' frames in
   h2s_frames y8{};
   y8.width = W, y8.height = H, y8.bits = 8, y8.location = H2S_LOC_DEVICE;
-  y8 = tight(&y8, base);
+  y8 = tight(&y8, base, H2S_LAYOUT_PLANAR);
   if (c->params.peak_detect) {
     // libplacebo branch: the reference converts each preview frame in its own
     // ffmpeg run (extract_frames_with_gpu_conversion_batch loops
@@ -1979,12 +1983,12 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
       }
       if ((e = hipMemsetAsync(c->d_pk, 0, pb, s)) != hipSuccess)
         return restored(queued_exit(c, s, hip_fail(c, e, "peak state reset")));
-      if ((rc = h2s_process(c, &fi, &fo, 1, hip_stream))) return restored(rc);
+      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_layout, H2S_LAYOUT_PLANAR))) return restored(rc);
     }
     if ((e = hipMemcpyAsync(c->d_pk, c->d_pk + 1, pb, hipMemcpyDeviceToDevice, s)) != hipSuccess)
       return queued_exit(c, s, hip_fail(c, e, "peak state restore"));
     if ((rc = peak_done(c, s))) return queued_exit(c, s, rc);
-  } else if ((rc = h2s_process(c, in, &y8, nframes, hip_stream))) {  // one launch for the batch
+  } else if ((rc = process_frames(c, in, &y8, nframes, s, c->in_layout, H2S_LAYOUT_PLANAR))) {  // one launch for the batch
     return rc;
   }
   hipError_t e = hipSuccess;

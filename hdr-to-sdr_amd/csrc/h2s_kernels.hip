@@ -356,34 +356,32 @@ __global__ __launch_bounds__(256) void k_chroma_bicubic(const KParams P, const C
 }
 
 // ---- host-side launchers (called from h2s_api.hip) ----------------------
-hipError_t launch_process(const KParams& P, bool vec, bool out8, hipStream_t s) {
-  constexpr int QPT = 4;
+enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2s_api.hip declares it
+
+// k_process's instance for the launch, one runtime flag per step into the
+// template arguments (VEC, OUT8, C444, DYN, LPX)
+template <bool VEC, bool OUT8, bool C444, bool DYN, bool LPX>
+static void launch_k(const KParams& P, dim3 grid, hipStream_t s) {
+  if constexpr (!(VEC && (C444 || DYN)))   // no such instances: launch_process clears VEC for them
+    hipLaunchKernelGGL((k_process<4, VEC, OUT8, C444, DYN, LPX>), grid, dim3(256), 0, s, P);
+}
+template <bool... B, class... Flags>
+static void launch_k(const KParams& P, dim3 grid, hipStream_t s, bool flag, Flags... rest) {
+  flag ? launch_k<B..., true>(P, grid, s, rest...) : launch_k<B..., false>(P, grid, s, rest...);
+}
+
+// the generic kernel over the launch's column groups (P.gx0, P.ngx).  form
+// (enum ProcessForm, h2s_api.hip): PF_VEC the rows allow vector accesses,
+// PF_OUT8 8-bit output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma
+// into P.chr444).  P.cv: dynamic peak, the frame's curve record on the device;
+// the libplacebo branch runs its exact path (h2s_lpx.h).  Dynamic-peak and
+// C444 launches are never VEC
+hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s) {
   const long long nb = (P.total + 255) / 256;
   if (nb == 0) return hipSuccess;
-  dim3 grid((unsigned)nb), block(256);
-  if (P.pipe == PIPE_LIBPLACEBO) {   // the libplacebo branch's exact path (h2s_lpx.h)
-    if (P.cv) {
-      if (out8) hipLaunchKernelGGL((k_process<QPT, false, true, false, true, true>), grid, block, 0, s, P);
-      else hipLaunchKernelGGL((k_process<QPT, false, false, false, true, true>), grid, block, 0, s, P);
-    } else if (vec) {
-      if (out8) hipLaunchKernelGGL((k_process<QPT, true, true, false, false, true>), grid, block, 0, s, P);
-      else hipLaunchKernelGGL((k_process<QPT, true, false, false, false, true>), grid, block, 0, s, P);
-    } else {
-      if (out8) hipLaunchKernelGGL((k_process<QPT, false, true, false, false, true>), grid, block, 0, s, P);
-      else hipLaunchKernelGGL((k_process<QPT, false, false, false, false, true>), grid, block, 0, s, P);
-    }
-    return hipGetLastError();
-  }
-  if (P.cv) {   // dynamic peak: the frame's curve record on the device
-    if (out8) hipLaunchKernelGGL((k_process<QPT, false, true, false, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_process<QPT, false, false, false, true>), grid, block, 0, s, P);
-  } else if (vec) {
-    if (out8) hipLaunchKernelGGL((k_process<QPT, true, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_process<QPT, true, false>), grid, block, 0, s, P);
-  } else {
-    if (out8) hipLaunchKernelGGL((k_process<QPT, false, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_process<QPT, false, false>), grid, block, 0, s, P);
-  }
+  const bool c444 = form & PF_C444, dyn = P.cv != nullptr;
+  launch_k<>(P, dim3((unsigned)nb), s, (form & PF_VEC) && !c444 && !dyn, (form & PF_OUT8) != 0, c444, dyn,
+             P.pipe == PIPE_LIBPLACEBO);
   return hipGetLastError();
 }
 
@@ -396,34 +394,6 @@ hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s) 
     case 3: hipLaunchKernelGGL((k_debug<3>), grid, block, 0, s, P, out); break;
     case 4: hipLaunchKernelGGL((k_debug<4>), grid, block, 0, s, P, out); break;
     default: hipLaunchKernelGGL((k_debug<5>), grid, block, 0, s, P, out); break;
-  }
-  return hipGetLastError();
-}
-
-// BICUBIC chroma, pass 1 on the generic kernel: k_process<C444> (luma +
-// per-pixel chroma) over the launch's column groups (P.gx0, P.ngx)
-hipError_t launch_process_c444(const KParams& P, bool out8, hipStream_t s) {
-  constexpr int QPT = 4;
-  const long long nb = (P.total + 255) / 256;
-  if (nb == 0) return hipSuccess;
-  if (P.pipe == PIPE_LIBPLACEBO) {   // the libplacebo branch's exact path (h2s_lpx.h)
-    if (P.cv) {
-      if (out8) hipLaunchKernelGGL((k_process<QPT, false, true, true, true, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-      else hipLaunchKernelGGL((k_process<QPT, false, false, true, true, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-    } else if (out8) {
-      hipLaunchKernelGGL((k_process<QPT, false, true, true, false, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-    } else {
-      hipLaunchKernelGGL((k_process<QPT, false, false, true, false, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-    }
-    return hipGetLastError();
-  }
-  if (P.cv) {   // dynamic peak: the frame's curve record on the device
-    if (out8) hipLaunchKernelGGL((k_process<QPT, false, true, true, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((k_process<QPT, false, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-  } else if (out8) {
-    hipLaunchKernelGGL((k_process<QPT, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
-  } else {
-    hipLaunchKernelGGL((k_process<QPT, false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, P);
   }
   return hipGetLastError();
 }

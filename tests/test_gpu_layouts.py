@@ -176,7 +176,9 @@ def reference(tm, params, name, kw, size, kind='tight'):
     'tight' batches (row-aligned surfaces at 200 wide, see above); 'aligned':
     planar surfaces with 16-byte aligned rows on both sides, the planar
     counterpart of a decoder's padded surface (the tile kernel from 64 pixels
-    of width up); 'generic': the generic kernel only (H2S_OPT_FAST_PATH 0)."""
+    of width up); 'generic': the generic kernel only (H2S_OPT_FAST_PATH 0);
+    any other name: tight batches again, kept apart for a caller whose `tm`
+    runs the chain under other parameters (a Previewer's)."""
     key = (name, size, kind)
     if key not in _results:
         if kind == 'generic':
@@ -381,6 +383,31 @@ def test_preview_identical(size, use_gpu):
         many = pv.convert_batch(semi, 'iw', 'ih')
         for got, want in zip(many, pv.convert_batch(planar, 'iw', 'ih')):
             assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize('size', [(192, 96), (70, 34)], ids=lambda s: f'{s[0]}x{s[1]}')
+@pytest.mark.parametrize('use_gpu', [False, True])
+def test_preview_on_semi_output_context(size, use_gpu):
+    """A preview's chain output is the call's own planar scratch whatever
+    layout the context writes its callers' frames in: the images equal those
+    of a context whose output layout was never changed, and that layout is
+    still the context's afterwards."""
+    name, kw = 'hable_lut_g22', CHAINS['hable_lut_g22']
+    planar = source(name, kw, size).to_torch('cuda')
+    with hdr2sdr.preview.Previewer(0, tonemapper='hable', lattice=lattice(), use_gpu=use_gpu) as fresh:
+        one = fresh.convert(planar, 96, 54, gamma=1.2)
+        many = fresh.convert_batch(planar, 'iw', 'ih')
+        want = reference(fresh._tm, fresh.params, name, kw, size, f'preview{int(use_gpu)}').to_layout('semi')
+    with hdr2sdr.preview.Previewer(0, tonemapper='hable', lattice=lattice(), use_gpu=use_gpu) as pv:
+        pv._tm.set_frame_layout('planar', 'semi')
+        assert np.array_equal(pv.convert(planar, 96, 54, gamma=1.2), one)
+        got = pv.convert_batch(planar, 'iw', 'ih')
+        assert len(got) == len(many) == F
+        for a, b in zip(got, many):
+            assert np.array_equal(a, b)
+        assert pv._tm._layouts == ('planar', 'semi')     # so process below sends the context no new layout
+        dst = device_dest(F, size, pv.params.bits_out, 'semi')
+        assert np.array_equal(run(pv._tm, pv.params, planar, dst).to_numpy().buf, want.buf)
 
 
 @pytest.mark.parametrize('size', [(192, 96), (200, 64), (70, 34)], ids=lambda s: f'{s[0]}x{s[1]}')
