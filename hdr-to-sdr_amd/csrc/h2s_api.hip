@@ -22,7 +22,8 @@ enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2
 hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s);
 hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s);
 bool fast_supported(int tonemap);
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg = 0);
+hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg = 0,
+                       int sub = 0);
 hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float* wy8, bool out8, hipStream_t s);
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st);
 hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
@@ -182,6 +183,8 @@ struct __attribute__((visibility("hidden"))) h2s_ctx {
   bool lp_exact = false;  // H2S_OPT_LP_EXACT
   // h2s_set_frame_layout: how later calls read `in` and write `out` (enum h2s_layout)
   int in_layout = H2S_LAYOUT_PLANAR, out_layout = H2S_LAYOUT_PLANAR;
+  // h2s_set_input_subsampling: the chroma subsampling later calls read `in` with (enum h2s_subsampling)
+  int in_sub = H2S_SUB_420;
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
@@ -608,18 +611,25 @@ bool aligned(const void* p, long long a) { return ((uintptr_t)p % (uintptr_t)a) 
 // semi (here and below): the set's layout (enum h2s_layout, never defaulted);
 // semi-planar (H2S_LAYOUT_SEMI): plane 1 holds (Cb, Cr) pairs, a row of it is
 // as long as a luma row, plane 2 is unused
-int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi) {
+// sub (here and below): an input set's chroma subsampling (enum
+// h2s_subsampling; output sets are 4:2:0): chroma planes of width >> cxs
+// samples x height >> cys rows
+int sub_cxs(int sub) { return sub == H2S_SUB_444 ? 0 : 1; }
+int sub_cys(int sub) { return sub == H2S_SUB_420 ? 1 : 0; }
+
+int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi, int sub = H2S_SUB_420) {
   if (!f) return fail(c, H2S_E_INVALID_ARG, std::string(which) + " frames is NULL");
   if (f->width <= 0 || f->height <= 0) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": empty frame");
   if ((f->width & 1) || (f->height & 1))
-    return fail(c, H2S_E_UNSUPPORTED, std::string(which) + ": 4:2:0 frames need even width and height");
+    return fail(c, H2S_E_UNSUPPORTED, std::string(which) + (sub ? ": the 4:2:0 output needs even width and height"
+                                                                 : ": 4:2:0 frames need even width and height"));
   if (f->bits != bits)
     return fail(c, H2S_E_INVALID_ARG,
                 std::string(which) + ": bits " + std::to_string(f->bits) + " != params " + std::to_string(bits));
   if (f->location != H2S_LOC_DEVICE && f->location != H2S_LOC_HOST)
     return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": bad location");
   const int bps = bits == 8 ? 1 : 2;
-  const long long crow = (long long)f->width / 2 * bps * (semi ? 2 : 1);
+  const long long crow = (long long)(f->width >> sub_cxs(sub)) * bps * (semi ? 2 : 1);
   const long long rowb[3] = {(long long)f->width * bps, crow, crow};
   for (int p = 0; p < (semi ? 2 : 3); p++) {
     if (!f->data[p]) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": NULL plane");
@@ -635,8 +645,9 @@ int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, i
 
 // vector path needs 16-B luma / 8-B chroma alignment of every row start
 // (semi-planar: four pairs of the interleaved plane are one luma-sized access)
-bool vec_ok(const h2s_frames* f, bool out8, int semi) {
-  const long long ay = out8 ? 8 : 16, ac = semi ? ay : (out8 ? 4 : 8);
+// (4:4:4 input: a chroma row is read like a luma row)
+bool vec_ok(const h2s_frames* f, bool out8, int semi, int sub = H2S_SUB_420) {
+  const long long ay = out8 ? 8 : 16, ac = semi || sub == H2S_SUB_444 ? ay : (out8 ? 4 : 8);
   const long long a[3] = {ay, ac, ac};
   for (int p = 0; p < (semi ? 2 : 3); p++)
     if (!aligned(f->data[p], a[p]) || f->linesize[p] % a[p] || f->frame_pitch[p] % a[p]) return false;
@@ -660,24 +671,24 @@ bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, int
   return true;
 }
 
-size_t frame_bytes(const h2s_frames* f) {
-  const size_t bps = f->bits == 8 ? 1 : 2;
-  return (size_t)f->width * f->height * bps * 3 / 2;
+size_t frame_bytes(const h2s_frames* f, int sub = H2S_SUB_420) {
+  const size_t bps = f->bits == 8 ? 1 : 2, ysz = (size_t)f->width * f->height * bps;
+  return ysz + 2 * (ysz >> (sub_cxs(sub) + sub_cys(sub)));
 }
 
 // tight device copy descriptor laid out in `base`
 // (semi-planar: the interleaved plane takes the two chroma planes' place,
 // so a frame's bytes are the same)
-h2s_frames tight(const h2s_frames* f, void* base, int semi) {
+h2s_frames tight(const h2s_frames* f, void* base, int semi, int sub = H2S_SUB_420) {
   h2s_frames t = *f;
   const long long bps = f->bits == 8 ? 1 : 2;
-  const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4;
+  const long long ysz = (long long)f->width * f->height * bps, csz = ysz >> (sub_cxs(sub) + sub_cys(sub));
   const long long fb = ysz + 2 * csz;
   t.data[0] = base;
   t.data[1] = (uint8_t*)base + ysz;
   t.data[2] = (uint8_t*)base + ysz + csz;
   t.linesize[0] = f->width * bps;
-  t.linesize[1] = t.linesize[2] = f->width / 2 * bps;
+  t.linesize[1] = t.linesize[2] = (f->width >> sub_cxs(sub)) * bps;
   t.frame_pitch[0] = t.frame_pitch[1] = t.frame_pitch[2] = fb;
   if (semi) t.data[2] = nullptr, t.linesize[1] = f->width * bps, t.linesize[2] = 0, t.frame_pitch[2] = 0;
   t.location = H2S_LOC_DEVICE;
@@ -685,30 +696,33 @@ h2s_frames tight(const h2s_frames* f, void* base, int semi) {
 }
 
 // the set the kernels bind: a device set itself, a host set's tight copy staged in `base`
-h2s_frames device_view(const h2s_frames* f, void* base, int semi) {
-  return f->location == H2S_LOC_HOST ? tight(f, base, semi) : *f;
+h2s_frames device_view(const h2s_frames* f, void* base, int semi, int sub = H2S_SUB_420) {
+  return f->location == H2S_LOC_HOST ? tight(f, base, semi, sub) : *f;
 }
 
 // the whole batch is one contiguous span laid out as tight() describes
-bool is_tight(const h2s_frames* f, int semi) {
+bool is_tight(const h2s_frames* f, int semi, int sub = H2S_SUB_420) {
   const long long bps = f->bits == 8 ? 1 : 2;
-  const long long ysz = (long long)f->width * f->height * bps, csz = ysz / 4, fb = ysz + 2 * csz;
+  const long long ysz = (long long)f->width * f->height * bps, csz = ysz >> (sub_cxs(sub) + sub_cys(sub)), fb = ysz + 2 * csz;
+  const long long cls = (f->width >> sub_cxs(sub)) * bps;
   if (semi)
     return f->linesize[0] == f->width * bps && f->linesize[1] == f->width * bps && f->frame_pitch[0] == fb &&
            f->frame_pitch[1] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz;
-  return f->linesize[0] == f->width * bps && f->linesize[1] == f->width / 2 * bps &&
-         f->linesize[2] == f->width / 2 * bps && f->frame_pitch[0] == fb && f->frame_pitch[1] == fb &&
+  return f->linesize[0] == f->width * bps && f->linesize[1] == cls &&
+         f->linesize[2] == cls && f->frame_pitch[0] == fb && f->frame_pitch[1] == fb &&
          f->frame_pitch[2] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz &&
          (const uint8_t*)f->data[2] == (const uint8_t*)f->data[1] + csz;
 }
 
-hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi) {
+hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi,
+                       int sub = H2S_SUB_420) {
   const long long bps = src->bits == 8 ? 1 : 2;
-  if (is_tight(src, semi) && is_tight(dst, semi))  // one DMA for the whole batch
+  if (is_tight(src, semi, sub) && is_tight(dst, semi, sub))  // one DMA for the whole batch
     return hipMemcpyAsync(dst->data[0], src->data[0], (size_t)src->frame_pitch[0] * nframes, hipMemcpyDefault, s);
   for (int fr = 0; fr < nframes; fr++)
     for (int p = 0; p < (semi ? 2 : 3); p++) {
-      const long long w = (p && !semi ? src->width / 2 : src->width) * bps, h = p ? src->height / 2 : src->height;
+      const long long w = (p && !semi ? src->width >> sub_cxs(sub) : src->width) * bps;
+      const long long h = p ? src->height >> sub_cys(sub) : src->height;
       hipError_t e = hipMemcpy2DAsync((uint8_t*)dst->data[p] + fr * dst->frame_pitch[p], dst->linesize[p],
                                       (const uint8_t*)src->data[p] + fr * src->frame_pitch[p], src->linesize[p], w,
                                       h, hipMemcpyDefault, s);
@@ -721,12 +735,15 @@ hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes
 // set is bound with plane 2 as plane 1 one sample on, samples two apart, so
 // the kernels address both layouts alike; 16-bit words carry the code in
 // their high bits
+// in_sub: the input's chroma subsampling (h2s_set_input_subsampling): its
+// chroma plane is icw x ich; cw, ch, ngx and total stay the output's
 void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes, int in_semi,
-                   int out_semi) {
+                   int out_semi, int in_sub = H2S_SUB_420) {
   k->W = in->width;
   k->H = in->height;
   k->cw = in->width / 2;
   k->ch = in->height / 2;
+  k->sub = in_sub, k->icw = in->width >> sub_cxs(in_sub), k->ich = in->height >> sub_cys(in_sub);
   k->ngx = (k->cw + 3) / 4;
   k->nframes = nframes;
   k->total = (long long)nframes * k->ch * k->ngx;
@@ -1169,6 +1186,7 @@ struct Route {
   bool vec, out8;
   int in_layout, out_layout;   // enum h2s_layout
   hipStream_t s;
+  int in_sub = H2S_SUB_420;    // enum h2s_subsampling
   bool tile() const { return path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL; }
   Route on(hipStream_t other) const {
     Route r = *this;
@@ -1211,10 +1229,11 @@ static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& 
   // the chroma right halo of the last tile reads the real column (F.cw stays
   // the frame's), so the split from the ragged columns is exact
   F.W = tiled_width(k), F.H = k.H, F.cw = k.cw, F.ch = k.ch;
+  F.icw = k.icw, F.ich = k.ich;
   F.chroma_edge = k.chroma_edge;
   F.in_semi = k.in_cstep == 2, F.in_sh = k.in_sh, F.out_semi = k.out_cstep == 2, F.out_sh = k.out_sh;
   for (int p = 0; p < 3; p++) {
-    const long long ib = (long long)(p ? k.ch : k.H) * k.in_ls[p], ob = (long long)(p ? k.ch : k.H) * k.out_ls[p];
+    const long long ib = (long long)(p ? k.ich : k.H) * k.in_ls[p], ob = (long long)(p ? k.ch : k.H) * k.out_ls[p];
     F.in_bytes[p] = (int)(ib < 0x7fffffff ? ib : 0x7fffffff);
     F.out_bytes[p] = (int)(ob < 0x7fffffff ? ob : 0x7fffffff);
   }
@@ -1231,7 +1250,7 @@ static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& 
   F.chr_w = k.W;
   F.inv_c56 = 1.0f / F.c56;
   const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
-  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, o.dbg);
+  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, o.dbg, k.sub);
 }
 
 // the generic kernel over a column range of k's frames: every column, or the
@@ -1309,6 +1328,21 @@ static int choose_path(const h2s_ctx* c, const KParams& k, const h2s_frames* din
   if (fast_params_ok(c, k) && tile_ok(din, dout, out8, tw, k.in_cstep == 2, k.out_cstep == 2))
     return (din->width & (tw - 1)) ? H2S_PATH_TILE_TAIL : H2S_PATH_TILE;
   return c->params.chroma_filter == H2S_CHROMA_BICUBIC ? H2S_PATH_TWO_PASS : H2S_PATH_GENERIC;
+}
+
+// what a 4:2:2 / 4:4:4 input set (h2s_set_input_subsampling) does not run
+// with: each is refused, none is routed to something else.  k: resolved
+static int check_subsampling(h2s_ctx* c, const KParams& k, int in_layout, int in_sub) {
+  if (in_sub == H2S_SUB_420) return 0;
+  if (in_layout == H2S_LAYOUT_SEMI)
+    return fail(c, H2S_E_UNSUPPORTED, "4:2:2 / 4:4:4 input is planar only (semi-planar p210 / p410 input is not supported)");
+  if (k.pipe == h2s::PIPE_LIBPLACEBO)
+    return fail(c, H2S_E_UNSUPPORTED,
+                "4:2:2 / 4:4:4 input runs on the CPU chain only: the libplacebo pipeline (and its peak detection) "
+                "uploads 4:2:0 (format=p010)");
+  if (c->params.peak_detect && (k.tonemap == H2S_TM_BT2390 || k.tonemap == H2S_TM_SPLINE))
+    return fail(c, H2S_E_UNSUPPORTED, "4:2:2 / 4:4:4 input: peak detection reads 4:2:0 input only");
+  return 0;
 }
 
 static int ensure_chr(h2s_ctx* c, const KParams& k) {
@@ -1541,6 +1575,8 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   KParams k;
   int rc = prepare(c, &k, false);  // the statistics need no LUT
   if (rc) return rc;
+  if (c->in_sub != H2S_SUB_420)
+    return fail(c, H2S_E_UNSUPPORTED, "h2s_peak_stats reads 4:2:0 input only (h2s_set_input_subsampling is 4:2:2 / 4:4:4)");
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
   if (in->location != H2S_LOC_DEVICE) return fail(c, H2S_E_INVALID_ARG, "h2s_peak_stats takes device frames");
   if (nframes == 0) return 0;
@@ -1612,13 +1648,13 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     const h2s_frames ci = frames_at(&din, f0), co = frames_at(&dout, f0);
     if (host_in) {
       const h2s_frames hi = frames_at(in, f0);
-      if ((e = copy_frames(&ci, &hi, nf, s_in, r.in_layout)) != hipSuccess) what = "host->device copy";
+      if ((e = copy_frames(&ci, &hi, nf, s_in, r.in_layout, r.in_sub)) != hipSuccess) what = "host->device copy";
       else if ((e = hipEventRecord(c->pev[i].ev, s_in)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       if (what) break;
     }
     if (i == 0) timing_begin(c, s_cmp);
-    fill_geometry(&k, &ci, &co, nf, r.in_layout, r.out_layout);
+    fill_geometry(&k, &ci, &co, nf, r.in_layout, r.out_layout, r.in_sub);
     if (dyn_peak) {
       if (int rc = run_dynamic_peak(c, k, r.on(s_cmp))) {
         sync_all();
@@ -1651,14 +1687,16 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
 
 // h2s_process for the two layouts given (the context's own for its callers'
 // sets; a preview's chain output is planar whatever the context's is).
-// Nothing it calls reads c->in_layout / c->out_layout
+// Nothing it calls reads c->in_layout / c->out_layout / c->in_sub
+// (in_sub: the input's chroma subsampling, the context's for every caller)
 static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
-                          int in_layout, int out_layout) {
+                          int in_layout, int out_layout, int in_sub) {
   if (nframes < 0) return fail(c, H2S_E_INVALID_ARG, "nframes < 0");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_layout))) return rc;
+  if ((rc = check_subsampling(c, k, in_layout, in_sub))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_layout, in_sub))) return rc;
   if ((rc = check_frames(c, out, c->params.bits_out, "output", out_layout))) return rc;
   if (in->width != out->width || in->height != out->height)
     return fail(c, H2S_E_INVALID_ARG, "input and output frame sizes differ");
@@ -1668,15 +1706,16 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
 
   // host sets are staged: input, then (256-byte aligned) output
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
-  const size_t ib = host_in ? (frame_bytes(in) * nframes + 255) / 256 * 256 : 0;
+  const size_t ib = host_in ? (frame_bytes(in, in_sub) * nframes + 255) / 256 * 256 : 0;
   const size_t ob = host_out ? frame_bytes(out) * nframes : 0;
   if ((host_in || host_out) && (rc = c->d_stage.reserve(c, ib + ob, "staging"))) return rc;
-  const h2s_frames din = device_view(in, c->d_stage, in_layout), dout = device_view(out, c->d_stage + ib, out_layout);
-  fill_geometry(&k, &din, &dout, nframes, in_layout, out_layout);
+  const h2s_frames din = device_view(in, c->d_stage, in_layout, in_sub), dout = device_view(out, c->d_stage + ib, out_layout);
+  fill_geometry(&k, &din, &dout, nframes, in_layout, out_layout, in_sub);
   // fast path: the tile kernel over whole 64 x 32 tiles; the generic kernel
   // covers the rest (choose_path / fast_params_ok) and the ragged columns
-  const Route r{choose_path(c, k, &din, &dout, out8), vec_ok(&din, false, in_layout) && vec_ok(&dout, out8, out_layout),
-                out8, in_layout, out_layout, s};
+  const Route r{choose_path(c, k, &din, &dout, out8),
+                vec_ok(&din, false, in_layout, in_sub) && vec_ok(&dout, out8, out_layout),
+                out8, in_layout, out_layout, s, in_sub};
   if (r.tile() && k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) return rc;
   // BICUBIC chroma (generic two-pass, or k_tile pass 1) uses the context scratch
   const bool two_pass = c->params.chroma_filter == H2S_CHROMA_BICUBIC;
@@ -1694,7 +1733,7 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
   if ((host_in || host_out) && nframes > 1 && !c->serial_host)
     return process_pipelined(c, k, in, out, din, dout, r, dyn_peak);
   if (host_in) {
-    hipError_t e = copy_frames(&din, in, nframes, s, in_layout);
+    hipError_t e = copy_frames(&din, in, nframes, s, in_layout, in_sub);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "host->device copy"));
   }
   timing_begin(c, s);
@@ -1726,7 +1765,7 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
 
 int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, void* hip_stream) {
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
-  return process_frames(c, in, out, nframes, (hipStream_t)hip_stream, c->in_layout, c->out_layout);
+  return process_frames(c, in, out, nframes, (hipStream_t)hip_stream, c->in_layout, c->out_layout, c->in_sub);
 }
 
 int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb, int out_location,
@@ -1737,7 +1776,8 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
+  if ((rc = check_subsampling(c, k, c->in_layout, c->in_sub))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub))) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t npx = (size_t)in->width * in->height, ob = npx * 3 * sizeof(float);
@@ -1745,24 +1785,26 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   // (host output) and one output frame for the tile kernel's own stores
   h2s_frames fo{};
   fo.width = in->width, fo.height = in->height, fo.bits = c->params.bits_out, fo.location = H2S_LOC_DEVICE;
-  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in) + 255) / 256 * 256 : 0;
+  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in, c->in_sub) + 255) / 256 * 256 : 0;
   const size_t fb = (frame_bytes(&fo) + 255) / 256 * 256, pb = out_location == H2S_LOC_HOST ? ob : 0;
   Dev<uint8_t> scratch;  // freed on every exit, after s has been waited for
   if ((rc = scratch.reserve(c, ib + fb + pb + 256, "debug"))) return rc;
   uint8_t* base = scratch;
-  const h2s_frames din = device_view(in, base, c->in_layout);
+  const h2s_frames din = device_view(in, base, c->in_layout, c->in_sub);
   hipError_t e;
-  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_layout)) != hipSuccess)
+  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_layout, c->in_sub)) != hipSuccess)
     return hip_fail(c, e, "debug copy");
   fo = tight(&fo, base + ib, H2S_LAYOUT_PLANAR);   // (the call's own planar scratch frame)
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
-  fill_geometry(&k, &din, &fo, 1, c->in_layout, H2S_LAYOUT_PLANAR);
+  fill_geometry(&k, &din, &fo, 1, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub);
   const bool out8 = c->params.bits_out == 8;
-  const Route r{choose_path(c, k, &din, &fo, out8), false, out8, c->in_layout, H2S_LAYOUT_PLANAR, s};
+  const Route r{choose_path(c, k, &din, &fo, out8), false, out8, c->in_layout, H2S_LAYOUT_PLANAR, s, c->in_sub};
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
+  // (4:2:0 input: there are no debug instances of the tile kernel for 4:2:2 /
+  // 4:4:4 input, whose planes are the generic kernel's whatever the path)
   e = h2s::launch_debug(k, stage, dout, s);
-  if (e == hipSuccess && r.tile()) {
+  if (e == hipSuccess && r.tile() && c->in_sub == H2S_SUB_420) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
       return rc;
@@ -1824,17 +1866,27 @@ int h2s_set_frame_layout(h2s_ctx* c, int in_layout, int out_layout) {
   return 0;
 }
 
+int h2s_set_input_subsampling(h2s_ctx* c, int subsampling) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  if (subsampling != H2S_SUB_420 && subsampling != H2S_SUB_422 && subsampling != H2S_SUB_444)
+    return fail(c, H2S_E_INVALID_ARG, "unknown chroma subsampling");
+  // (only the arguments of later launches change: nothing queued reads this)
+  c->in_sub = subsampling;
+  return 0;
+}
+
 int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
+  if ((rc = check_subsampling(c, k, c->in_layout, c->in_sub))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub))) return rc;
   if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_layout))) return rc;
   // host sets are staged into tight device copies, whose alignment decides
   uint8_t* fake = (uint8_t*)(uintptr_t)4096;
-  const h2s_frames din = device_view(in, fake, c->in_layout), dout = device_view(out, fake, c->out_layout);
-  fill_geometry(&k, &din, &dout, 1, c->in_layout, c->out_layout);
+  const h2s_frames din = device_view(in, fake, c->in_layout, c->in_sub), dout = device_view(out, fake, c->out_layout);
+  fill_geometry(&k, &din, &dout, 1, c->in_layout, c->out_layout, c->in_sub);
   return choose_path(c, k, &din, &dout, c->params.bits_out == 8);
 }
 
@@ -1895,7 +1947,7 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
   if (!c->params_set) return fail(c, H2S_E_INVALID_ARG, "h2s_set_params was not called");
   if (c->params.bits_out != 8)
     return fail(c, H2S_E_INVALID_ARG, "preview needs params.bits_out == 8 (the chain's yuv420p)");
-  int rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout);
+  int rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub);
   if (rc) return rc;
   const int W = in->width, H = in->height;
   const bool scale = out_w != W || out_h != H;
@@ -1983,12 +2035,12 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
       }
       if ((e = hipMemsetAsync(c->d_pk, 0, pb, s)) != hipSuccess)
         return restored(queued_exit(c, s, hip_fail(c, e, "peak state reset")));
-      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_layout, H2S_LAYOUT_PLANAR))) return restored(rc);
+      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub))) return restored(rc);
     }
     if ((e = hipMemcpyAsync(c->d_pk, c->d_pk + 1, pb, hipMemcpyDeviceToDevice, s)) != hipSuccess)
       return queued_exit(c, s, hip_fail(c, e, "peak state restore"));
     if ((rc = peak_done(c, s))) return queued_exit(c, s, rc);
-  } else if ((rc = process_frames(c, in, &y8, nframes, s, c->in_layout, H2S_LAYOUT_PLANAR))) {  // one launch for the batch
+  } else if ((rc = process_frames(c, in, &y8, nframes, s, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub))) {  // one launch for the batch
     return rc;
   }
   hipError_t e = hipSuccess;

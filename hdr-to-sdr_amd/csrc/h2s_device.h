@@ -17,7 +17,7 @@ namespace h2s {
 struct CurveConsts;
 
 struct KParams {
-  // geometry (luma W x H, chroma cw x ch, ngx groups of QPT chroma columns)
+  // geometry (luma W x H, output chroma cw x ch, ngx groups of QPT chroma columns)
   int W, H, cw, ch, ngx;
   int nframes;
   long long total;  // nframes * ch * ngx work items
@@ -102,6 +102,10 @@ struct KParams {
   // constants derive from, npl, tm_param (NaN: default), bits_in - 8
   double x_peak, x_avg, x_npl, x_tm_param;
   int x_sh;
+  // the input's chroma subsampling (h2s_set_input_subsampling: 0 = 4:2:0, 1 =
+  // 4:2:2, 2 = 4:4:4) and its chroma plane icw x ich (W/2 x H/2, W/2 x H, W x
+  // H).  cw, ch, ngx and total above are the output side's, always W/2 x H/2
+  int sub, icw, ich;
 };
 
 constexpr int PIPE_CPU = 1, PIPE_LIBPLACEBO = 2;
@@ -246,6 +250,11 @@ struct FastParams : CurveConsts {
   // in_mask2 (which then also clears the bits that cross the halves of a word
   // pair); output codes are shifted up by out_sh
   int in_semi, in_sh, out_semi, out_sh;
+  // 4:2:2 / 4:4:4 input (h2s_set_input_subsampling), read by the k_tile<...,
+  // SUB> instances only (last again, so that no other field moves): the
+  // input's chroma plane is icw x ich samples (W/2 x H, or W x H); cw and ch
+  // above stay the output's W/2 x H/2
+  int icw, ich;
 };
 
 constexpr int TBW = 64, TBH = 32;   // k_tile: luma tile of one block

@@ -31,6 +31,9 @@ H2S_TILE_EXTERN(4, 0, true)
 H2S_TILE_EXTERN(4, 1, true)
 H2S_TILE_EXTERN(5, 0, true)
 H2S_TILE_EXTERN(5, 1, true)
+// the instances for 4:2:2 / 4:4:4 input (h2s_fast_sub422.hip, h2s_fast_sub444.hip)
+H2S_TILE_SUB_EXTERN(1)
+H2S_TILE_SUB_EXTERN(2)
 
 // YUV-premultiplied lattice (12-byte records, .cube order):
 // ((16 + 219*Y)*s + 0.5, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
@@ -60,7 +63,9 @@ bool fast_supported(int tonemap) { return tonemap >= 4 && tonemap <= 8; }
 // libplacebo curves have none).  lp: the libplacebo branch (every operator).
 // dbg: 0 = the
 // product kernel; 1..5 = its debug instance for that h2s_stage (F.dbg set)
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg) {
+// sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4: CPU chain product
+// instances only; anything else there is an error, never another kernel)
+hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg, int sub) {
   const long long nt = (long long)F.nbx * F.nby * F.nframes;
   if (nt == 0) return hipSuccess;
   const long long nb = (nt + F.tpb - 1) / F.tpb;
@@ -72,6 +77,11 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   if (tm == 7 || tm == 8 || lp) desat = 0;
   // planar sets on both sides: the instances without the layout branches
   const bool semi = F.in_semi || F.out_semi;
+  if (sub) {
+    if (lp || dbg || F.in_semi || sub > 2) return hipErrorInvalidValue;
+    return sub == 1 ? launch_tile<0, 0, true, 1>(F, trc, tm, desat, grid, lds, s)
+                    : launch_tile<0, 0, true, 2>(F, trc, tm, desat, grid, lds, s);
+  }
 #define H2S_DISPATCH(D)                                                                                  \
   if (semi)                                                                                              \
     return lp ? launch_tile<D, 1, true>(F, trc, tm, desat, grid, lds, s)                                 \

@@ -45,19 +45,26 @@ __device__ __forceinline__ int ldc(const KParams& P, const uint8_t* row, int x) 
 // chroma planes are then written by k_chroma_bicubic
 // LPX: the libplacebo branch, stages 1-3 in exact arithmetic (h2s_lpx.h)
 // from the integer codes (cc*: the chroma codes kept for it)
-template <int QPT, bool VEC, bool OUT8, bool C444 = false, bool DYN = false, bool LPX = false>
+// SUB: the input's chroma subsampling (P.sub; CPU chain, static peak): 1 =
+// 4:2:2, chroma rows 2cy and 2cy+1 of a W/2 x H plane through the horizontal
+// pass alone; 2 = 4:4:4, the pixel's own sample of a W x H plane.  The output
+// side (the work item, the 2x2 reduction, the stores) is 4:2:0 whatever SUB
+template <int QPT, bool VEC, bool OUT8, bool C444 = false, bool DYN = false, bool LPX = false, int SUB = 0>
 __global__ __launch_bounds__(256) void k_process(const KParams P0) {
+  static_assert(SUB == 0 || (!DYN && !LPX), "4:2:2 / 4:4:4 input: CPU chain, static peak");
   LpX X;
   auto body = [&](const KParams& P, const int f, const int cy, const int cx0) {
   const int cw = P.cw, ch = P.ch;
 
   // ---- chroma: rows cy-1, cy, cy+1; columns cx0 .. cx0+QPT (halo) ----
+  // (SUB 1: rows 2cy, 2cy+1 of the 4:2:2 plane, the same columns; SUB 2 below)
+  constexpr int NR = SUB ? 2 : 3;
   float cu[3][QPT + 1], cv[3][QPT + 1];
   int ccu[3][QPT + 1], ccv[3][QPT + 1];
-  const int crow[3] = {edge(P, cy - 1, ch), cy, edge(P, cy + 1, ch)};
+  const int crow[3] = {SUB ? 2 * cy : edge(P, cy - 1, ch), SUB ? 2 * cy + 1 : cy, edge(P, cy + 1, ch)};
   const bool full = cx0 + QPT <= cw;
 #pragma unroll
-  for (int i = 0; i < 3; i++) {
+  for (int i = 0; i < (SUB == 2 ? 0 : NR); i++) {
     const uint8_t* ru = P.in[1] + f * P.in_fp[1] + crow[i] * P.in_ls[1];
     const uint8_t* rv = P.in[2] + f * P.in_fp[2] + crow[i] * P.in_ls[2];
     if (VEC && full && QPT == 4) {
@@ -94,7 +101,7 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   // horizontal pass (left siting): h[2k] = c[k], h[2k+1] = (c[k] + c[k+1]) / 2
   float hu[3][2 * QPT], hv[3][2 * QPT];
 #pragma unroll
-  for (int i = 0; i < 3; i++)
+  for (int i = 0; i < (SUB == 2 ? 0 : NR); i++)
 #pragma unroll
     for (int k = 0; k < QPT; k++) {
       hu[i][2 * k] = cu[i][k];
@@ -105,6 +112,34 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
 
   // ---- luma: rows 2cy, 2cy+1; columns 2cx0 .. 2cx0+2QPT-1 ----
   const int x0 = 2 * cx0;
+  if constexpr (SUB == 2) {   // 4:4:4: chroma rows 2cy, 2cy+1, the luma columns; no resampling
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const uint8_t* ru = P.in[1] + f * P.in_fp[1] + (2 * cy + j) * P.in_ls[1];
+      const uint8_t* rv = P.in[2] + f * P.in_fp[2] + (2 * cy + j) * P.in_ls[2];
+      int cu4[2 * QPT], cv4[2 * QPT];
+      if (VEC && full && QPT == 4) {
+        const uint4 a = *reinterpret_cast<const uint4*>(ru + 2 * x0), b = *reinterpret_cast<const uint4*>(rv + 2 * x0);
+        const unsigned wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          cu4[2 * k] = code_of(P, wa[k] & 0xffff), cu4[2 * k + 1] = code_of(P, wa[k] >> 16);
+          cv4[2 * k] = code_of(P, wb[k] & 0xffff), cv4[2 * k + 1] = code_of(P, wb[k] >> 16);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 2 * QPT; k++) {
+          const int x = x0 + k < P.W ? x0 + k : P.W - 1;
+          cu4[k] = ldy(P, ru, x), cv4[k] = ldy(P, rv, x);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 2 * QPT; k++) {
+        hu[j][k] = (float)cu4[k] * P.c_scale + P.c_off;
+        hv[j][k] = (float)cv4[k] * P.c_scale + P.c_off;
+      }
+    }
+  }
   int ys[2][2 * QPT];
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -134,8 +169,9 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
 #pragma unroll
     for (int p = 0; p < 4; p++) {
       const int j = p >> 1, x = 2 * k + (p & 1);
-      const float cb = j == 0 ? 0.25f * hu[0][x] + 0.75f * hu[1][x] : 0.75f * hu[1][x] + 0.25f * hu[2][x];
-      const float cr = j == 0 ? 0.25f * hv[0][x] + 0.75f * hv[1][x] : 0.75f * hv[1][x] + 0.25f * hv[2][x];
+      // (SUB: no vertical pass; row j of the loaded pair is the pixel's own)
+      const float cb = SUB ? hu[j][x] : j == 0 ? 0.25f * hu[0][x] + 0.75f * hu[1][x] : 0.75f * hu[1][x] + 0.25f * hu[2][x];
+      const float cr = SUB ? hv[j][x] : j == 0 ? 0.25f * hv[0][x] + 0.75f * hv[1][x] : 0.75f * hv[1][x] + 0.25f * hv[2][x];
       const float yv = (float)ys[j][x] * P.y_scale + P.y_off;
       float r, g, b;
       const int px = 2 * (cx0 + k) + (p & 1), py = 2 * cy + j;
@@ -267,9 +303,10 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
   const long long npx = (long long)P.W * P.H;
   if (i >= npx) return;
   const int x = (int)(i % P.W), y = (int)(i / P.W);
-  const int cw = P.cw, ch = P.ch;
+  const int cw = P.icw, ch = P.ich;   // (the input's chroma plane: 4:2:0 W/2 x H/2)
   auto hpass = [&](int plane, int cyy) -> float {
     const uint8_t* row = P.in[plane] + edge(P, cyy, ch) * P.in_ls[plane];
+    if (P.sub == 2) return (float)ldc(P, row, x) * P.c_scale + P.c_off;   // 4:4:4: the pixel's own sample
     const int k = x >> 1;
     const float a = (float)ldc(P, row, edge(P, k, cw)) * P.c_scale + P.c_off;
     if (!(x & 1)) return a;
@@ -277,6 +314,7 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
     return 0.5f * a + 0.5f * b;
   };
   auto up = [&](int plane) -> float {
+    if (P.sub) return hpass(plane, y);   // 4:2:2 / 4:4:4: chroma row y, no vertical pass
     const int m = y >> 1;
     if (!(y & 1)) return 0.25f * hpass(plane, m - 1) + 0.75f * hpass(plane, m);
     return 0.75f * hpass(plane, m) + 0.25f * hpass(plane, m + 1);
@@ -360,14 +398,16 @@ enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2
 
 // k_process's instance for the launch, one runtime flag per step into the
 // template arguments (VEC, OUT8, C444, DYN, LPX)
-template <bool VEC, bool OUT8, bool C444, bool DYN, bool LPX>
+// (SUB first: the input's chroma subsampling, launch_process)
+template <int SUB, bool VEC, bool OUT8, bool C444, bool DYN, bool LPX>
 static void launch_k(const KParams& P, dim3 grid, hipStream_t s) {
-  if constexpr (!(VEC && (C444 || DYN)))   // no such instances: launch_process clears VEC for them
-    hipLaunchKernelGGL((k_process<4, VEC, OUT8, C444, DYN, LPX>), grid, dim3(256), 0, s, P);
+  // no such instances: launch_process clears VEC for them, and refuses SUB with DYN / LPX
+  if constexpr (!(VEC && (C444 || DYN)) && !(SUB && (DYN || LPX)))
+    hipLaunchKernelGGL((k_process<4, VEC, OUT8, C444, DYN, LPX, SUB>), grid, dim3(256), 0, s, P);
 }
-template <bool... B, class... Flags>
+template <int SUB, bool... B, class... Flags>
 static void launch_k(const KParams& P, dim3 grid, hipStream_t s, bool flag, Flags... rest) {
-  flag ? launch_k<B..., true>(P, grid, s, rest...) : launch_k<B..., false>(P, grid, s, rest...);
+  flag ? launch_k<SUB, B..., true>(P, grid, s, rest...) : launch_k<SUB, B..., false>(P, grid, s, rest...);
 }
 
 // the generic kernel over the launch's column groups (P.gx0, P.ngx).  form
@@ -379,9 +419,13 @@ static void launch_k(const KParams& P, dim3 grid, hipStream_t s, bool flag, Flag
 hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s) {
   const long long nb = (P.total + 255) / 256;
   if (nb == 0) return hipSuccess;
-  const bool c444 = form & PF_C444, dyn = P.cv != nullptr;
-  launch_k<>(P, dim3((unsigned)nb), s, (form & PF_VEC) && !c444 && !dyn, (form & PF_OUT8) != 0, c444, dyn,
-             P.pipe == PIPE_LIBPLACEBO);
+  const bool c444 = form & PF_C444, dyn = P.cv != nullptr, lpx = P.pipe == PIPE_LIBPLACEBO;
+  const bool vec = (form & PF_VEC) && !c444 && !dyn, out8 = (form & PF_OUT8) != 0;
+  // 4:2:2 / 4:4:4 input: CPU chain, static peak (h2s_api.hip refuses the rest)
+  if (P.sub && (dyn || lpx || P.sub > 2 || P.in_cstep != 1)) return hipErrorInvalidValue;
+  if (P.sub == 1) launch_k<1>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
+  else if (P.sub == 2) launch_k<2>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
+  else launch_k<0>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
   return hipGetLastError();
 }
 

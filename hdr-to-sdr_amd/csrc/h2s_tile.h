@@ -820,10 +820,16 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const uint8_t* base
 // one tile's global loads, held in registers between issue and the LDS commit
 // (semi-planar input, F.in_semi: ua = four (Cb, Cr) pairs of the interleaved
 // plane on threads t < 144, uh = the pair right of them; the same registers)
-template <bool SEMI>
+// (SUB 1, 4:2:2 input: the same registers, a chunk on every thread; SUB 2,
+// 4:4:4: one chunk of each chroma plane per thread and no halo)
+template <bool SEMI, int SUB = 0>
 struct TileRegs {
   uint4 ya, ua;     // luma chunk; chroma chunk of plane pc (threads tc < 72)
   std::conditional_t<SEMI, unsigned, uint16_t> uh;   // the chroma chunk's right-halo sample (SEMI: or pair)
+};
+template <bool SEMI>
+struct TileRegs<SEMI, 2> {
+  uint4 ya, ua, va;   // luma chunk; the Cb and Cr chunks under it
 };
 
 struct TileGeo {
@@ -895,15 +901,24 @@ __device__ __forceinline__ LaneOfs lane_ofs(const FastParams& F, int t) {
 // halo) lie inside the frame take the lane offsets of LaneOfs plus a scalar
 // origin; border tiles clamp per lane.  The chroma registers of threads >= 72
 // are left undefined (never committed).
-template <bool SEMI>
-__device__ __forceinline__ TileRegs<SEMI> tile_load(const FastParams& F, const TileGeo& g, int t, const LaneOfs& L) {
+// SUB (h2s_set_input_subsampling; 0 = 4:2:0, the text above): the chroma
+// window of a 4:2:2 / 4:4:4 input has the tile's own 32 rows and no halo rows,
+// so a bottom tile clamps its chroma rows as it clamps its luma rows.
+//  1 (4:2:2): 32 rows x 4 chunks per plane, and the right-halo sample of each
+//    row's last chunk: every thread loads one chunk, U on threads 0..127, V
+//    on 128..255 (LaneOfs::u as it is; the scalar origin is row py0, not
+//    cy0 - 1)
+//  2 (4:4:4): 32 rows x 8 chunks per plane, the luma chunk's own geometry:
+//    every thread loads the Cb and the Cr chunk under its luma chunk
+template <bool SEMI, int SUB = 0>
+__device__ __forceinline__ TileRegs<SEMI, SUB> tile_load(const FastParams& F, const TileGeo& g, int t, const LaneOfs& L) {
   // Every thread issues exactly one load of each kind whatever the tile: the
   // offsets are chosen per case and the loads follow the merge; threads
   // without a chroma chunk read out of range, which returns 0 and fetches
   // nothing
   const __amdgpu_buffer_rsrc_t iy = plane_rsrc(F.in[0] + g.f * F.in_fp[0], F.in_bytes[0]);
   const int yr = t >> 3, yc = t & 7;
-  TileRegs<SEMI> r;
+  TileRegs<SEMI, SUB> r;
   int vy, sy;
   if (g.py0 + TBH <= F.H) {   // block-uniform
     vy = L.y, sy = g.py0 * (int)F.in_ls[0] + 2 * g.px0;
@@ -911,6 +926,43 @@ __device__ __forceinline__ TileRegs<SEMI> tile_load(const FastParams& F, const T
     vy = (g.py0 + yr < F.H ? g.py0 + yr : F.H - 1) * (int)F.in_ls[0] + 2 * (g.px0 + 8 * yc), sy = 0;
   }
   r.ya = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(iy, vy, sy, NT));
+  if constexpr (SUB == 2) {
+    const __amdgpu_buffer_rsrc_t iu = plane_rsrc(F.in[1] + g.f * F.in_fp[1], F.in_bytes[1]);
+    const __amdgpu_buffer_rsrc_t iv = plane_rsrc(F.in[2] + g.f * F.in_fp[2], F.in_bytes[2]);
+    const int lu = (int)F.in_ls[1], lv = (int)F.in_ls[2];
+    int vu, vv, su, sv;
+    if (g.py0 + TBH <= F.H) {   // block-uniform
+      vu = yr * lu + 16 * yc, vv = yr * lv + 16 * yc;
+      su = g.py0 * lu + 2 * g.px0, sv = g.py0 * lv + 2 * g.px0;
+    } else {
+      const int row = g.py0 + yr < F.H ? g.py0 + yr : F.H - 1;
+      vu = row * lu + 2 * (g.px0 + 8 * yc), vv = row * lv + 2 * (g.px0 + 8 * yc), su = sv = 0;
+    }
+    r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(iu, vu, su, NT));
+    r.va = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(iv, vv, sv, NT));
+    return r;
+  } else if constexpr (SUB == 1) {
+    const int pc = __builtin_amdgcn_readfirstlane(t >> 7), tc = t & 127;
+    const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1 + pc] + g.f * F.in_fp[1 + pc], F.in_bytes[1 + pc]);
+    const int ls = (int)F.in_ls[1 + pc];
+    int vc, vh, sc;
+    if (g.py0 + TBH <= F.H && g.cx0 + CBW + 1 <= F.icw) {   // block-uniform
+      vc = L.u, vh = L.u + 16, sc = g.py0 * ls + 2 * g.cx0;
+    } else {
+      const int clr = tc >> 2, ccx = tc & 3;
+      const int row = g.py0 + clr < F.H ? g.py0 + clr : F.H - 1;
+      vc = row * ls + 2 * (g.cx0 + 8 * ccx);
+      vh = row * ls + 2 * chroma_edge_at(g.cx0 + 8 * ccx + 8, F.icw, F.chroma_edge);
+      sc = 0;
+    }
+    // only a row's last chunk has a halo the tile does not hold already (the
+    // others' is the next chunk's first sample): theirs is read out of range,
+    // which returns 0 and fetches nothing
+    if ((tc & 3) != 3) vh = 0x7FFFFFF0;
+    r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ic, vc, sc, NT));
+    r.uh = __builtin_amdgcn_raw_buffer_load_b16(ic, vh, sc, 0);
+    return r;
+  } else {
   if (SEMI && F.in_semi) {   // block-uniform
     // the interleaved plane: 18 rows x 8 chunks of four (Cb, Cr) pairs on
     // threads 0..143, each with the pair right of its chunk (4 bytes), so
@@ -949,6 +1001,7 @@ __device__ __forceinline__ TileRegs<SEMI> tile_load(const FastParams& F, const T
   r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ic, vc, sc, NT));
   r.uh = __builtin_amdgcn_raw_buffer_load_b16(ic, vh, sc, 0);
   return r;
+  }
 }
 
 // staging and store helpers of k_tile
@@ -1008,6 +1061,49 @@ __device__ __forceinline__ float stage_chroma_semi(float* plane_u, float* plane_
     *reinterpret_cast<float4*>(plane_v + o + 4 * k) =
         make_float4(v[2 * k] + v[2 * k], v[2 * k] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 1], v[2 * k + 1] + v[2 * k + 2]);
   }
+  return m;
+}
+// 4:2:2 input (SUB 1): the chunk's centred codes as they are (x1: the
+// horizontal pass runs in the step), row stride C422_ST floats; tt: row
+// tt >> 2, chunk tt & 3 of the tile's 32 x 4 chunks; a row's last chunk also
+// stores its right-halo sample h (column 32; the other chunks' h is not
+// loaded).  Returns the largest |centred code| of what the chunk stages, so
+// the tile's flag sees every staged sample
+constexpr int C422_ST = 36;   // 33 samples; rows 16-byte aligned, 8 rows of a step on distinct bank groups
+constexpr int C444_ST = 72;   // 4:4:4: 64 16-bit centred codes per row (+ pad: rows 36 banks apart)
+__device__ __forceinline__ float stage_chroma422(float* plane, uint4 a, unsigned h, int tt, float cmid) {
+  float v[9];
+  unpack8(a, v);
+  v[8] = (float)h;
+#pragma unroll
+  for (int k = 0; k < 9; k++) v[k] -= cmid;
+  float m = fabsf(v[0]);
+#pragma unroll
+  for (int k = 1; k < 8; k++) m = __builtin_fmaxf(m, fabsf(v[k]));
+  float* d = plane + (tt >> 2) * C422_ST + 8 * (tt & 3);
+  *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  if ((tt & 3) == 3) d[8] = v[8], m = __builtin_fmaxf(m, fabsf(v[8]));
+  return m;
+}
+// 4:4:4 input (SUB 2): a chunk of each plane as 16-bit centred codes (exact:
+// |code - mid| <= 2048), one 16-byte store per plane at (row, 8 col8)
+__device__ __forceinline__ float stage_chroma444(float* plane_u, float* plane_v, uint4 a, uint4 b, int row, int col8,
+                                                 int imid) {
+  auto pack = [&](uint4 q, float* plane, float& m) {
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    unsigned o[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int lo = (int)(w[k] & 0xffff) - imid, hi = (int)(w[k] >> 16) - imid;
+      m = __builtin_fmaxf(m, __builtin_fmaxf(fabsf((float)lo), fabsf((float)hi)));
+      o[k] = ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
+    }
+    *reinterpret_cast<uint4*>(reinterpret_cast<int16_t*>(plane) + row * C444_ST + 8 * col8) = make_uint4(o[0], o[1], o[2], o[3]);
+  };
+  float m = 0.0f;
+  pack(a, plane_u, m);
+  pack(b, plane_v, m);
   return m;
 }
 // luma codes of tile row r, chunk c (8 pixels), packed for one 16-byte (u16)
@@ -1128,7 +1224,15 @@ __device__ __forceinline__ void put_chroma_semi(const FastParams& F, const TileG
 // spilled SGPRs on the product instances): a launch with
 // planar sets on both sides runs the SEMI = false instance, which compiles
 // to what it was before the layouts existed
-template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false>
+// SUB (the input's chroma subsampling, h2s_set_input_subsampling): 1 = 4:2:2,
+// 2 = 4:4:4, CPU chain product instances only (LP 0, DBG 0; SEMI for the
+// output side).  The staged chroma keeps hrow's allocation (so the block's LDS
+// and the 5 blocks per CU): 4:2:2 as x1 centred floats, 32 rows of C422_ST,
+// with the horizontal pass in the step; 4:4:4 as 16-bit centred codes, 32
+// rows of C444_ST.  The step hands lin_tone the same x8 centred values (exact
+// small integers), so everything after S0 is the 4:2:0 instance's code.  The
+// SUB 0 instances compile to what they were before the parameter existed
+template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false, int SUB = 0>
 // 5 waves per SIMD = the LDS-bound occupancy (5 blocks of ~27.6 KB per CU;
 // 3, 4 and 6 measured slower on the bench content, 6 by 4.5 % in round 3 at
 // 80 VGPRs: profiles/r03/ablations/six_waves.log, blocks_per_cu.log): let
@@ -1144,7 +1248,9 @@ template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false>
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TILE_WPE_LP : H2S_TILE_WPE))) void k_tile(
     const FastParams F) {
+  static_assert(SUB == 0 || (LP == 0 && DBG == 0), "4:2:2 / 4:4:4 input: CPU chain product instances only");
   constexpr int YST = row_stride<LP>(), HST = YST;
+  static_assert(TBH * C422_ST <= (CBH + 2) * HST && TBH * C444_ST <= 2 * (CBH + 2) * HST, "hrow holds the SUB windows");
   __shared__ float yin[TBH * YST];             // luma samples x ys; output codes overwrite them in place
   __shared__ float hrow[2][(CBH + 2) * HST];   // chroma rows (halo incl.) upsampled x2 horizontally
   __shared__ float csum[2][CBH * CBW];         // per chroma sample: sum of its 2x2 pixel contributions
@@ -1167,7 +1273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   // ---- prologue: first tile + tables, all issued before any wait ----
   TileGeo geo = tile_geo(F, tile);
   const LaneOfs lofs = lane_ofs<SEMI>(F, t);
-  TileRegs<SEMI> cur = tile_load<SEMI>(F, geo, t, lofs);
+  TileRegs<SEMI, SUB> cur = tile_load<SEMI, SUB>(F, geo, t, lofs);
   const __amdgpu_buffer_rsrc_t req = __builtin_amdgcn_make_buffer_rsrc((void*)F.eq_lut, (short)0, 2 * F.eq_n, 0x00020000);
   const unsigned eq0 = __builtin_amdgcn_raw_buffer_load_b16(req, 2 * t, 0, 0);  // out of range -> 0
   float4 pq0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1217,6 +1323,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   const float* h0 = hrow[0] + (qy + 1) * HST + xl;
   const float* h1 = hrow[1] + (qy + 1) * HST + xl;
   const int hb = pyl ? HST : -HST;
+  // SUB 1: the pixel's own chroma row, sample xl >> 1 and (odd columns) the one right of it
+  const float* c0 = hrow[0] + yl * C422_ST + (xl >> 1);
+  const float* c1 = hrow[1] + yl * C422_ST + (xl >> 1);
+  // SUB 2: the pixel's own sample
+  const int16_t* s0 = reinterpret_cast<const int16_t*>(hrow[0]) + yl * C444_ST + xl;
+  const int16_t* s1 = reinterpret_cast<const int16_t*>(hrow[1]) + yl * C444_ST + xl;
   float* csb = csum[0] + qy * CBW + 8 * w + qx;
 
   // hot constants live in VGPRs for the whole kernel.  Staged samples:
@@ -1338,8 +1450,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
       H2S_MARK("S0 step: staged Y, vertical chroma");
       const float ybs = ybase[oy];
-      const float U = fmaf(3.0f, h0[oh], h0[oh + hb]);   // x8 upsampled, centred, exact
-      const float V = fmaf(3.0f, h1[oh], h1[oh + hb]);
+      float U, V;
+      if constexpr (SUB == 1) {   // 4 h at the pixel's row: 8 c[k], or 4 (c[k] + c[k+1])
+        const int oc = 8 * (s >> 1) * C422_ST + 4 * (s & 1);
+        U = 4.0f * (c0[oc] + c0[oc + pxl]), V = 4.0f * (c1[oc] + c1[oc + pxl]);
+      } else if constexpr (SUB == 2) {   // 8 (code - mid)
+        const int oc = 8 * (s >> 1) * C444_ST + 8 * (s & 1);
+        U = 8.0f * (float)s0[oc], V = 8.0f * (float)s1[oc];
+      } else {
+        U = fmaf(3.0f, h0[oh], h0[oh + hb]);   // x8 upsampled, centred, exact
+        V = fmaf(3.0f, h1[oh], h1[oh + hb]);
+      }
       const long long di = DBG && g.f == 0 && g.py0 + yl + 8 * (s >> 1) < F.H
                                ? (long long)(g.py0 + yl + 8 * (s >> 1)) * F.dbg_w + g.px0 + xl + 8 * (s & 1)
                                : -1;
@@ -1364,18 +1485,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       // semi-planar: the code sits in each 16-bit word's high bits; both
       // halves of a pair move down together and the mask (always set then)
       // clears what crossed from the high half, and the word's low junk bits
-      if constexpr (SEMI) {
+      if constexpr (SEMI && SUB == 0) {
         if (F.in_sh) {
           shift_in(cur.ya), shift_in(cur.ua);
           cur.uh >>= F.in_sh;
         }
       }
       mask_in(cur.ya), mask_in(cur.ua);
-      cur.uh &= F.in_mask2;
+      if constexpr (SUB == 2) mask_in(cur.va);
+      else cur.uh &= F.in_mask2;
     }
     const float my = stage_luma<YST>(yin, cur.ya, t >> 3, t & 7, ysc, yoff);
     float mc = 0.0f;
-    if (SEMI && F.in_semi) {   // block-uniform
+    if constexpr (SUB == 1) {
+      mc = stage_chroma422(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
+    } else if constexpr (SUB == 2) {
+      mc = stage_chroma444(hrow[0], hrow[1], cur.ua, cur.va, t >> 3, t & 7, (int)F.c_mid);
+    } else if (SEMI && F.in_semi) {   // block-uniform
       if (t < 144) mc = stage_chroma_semi<HST>(hrow[0], hrow[1], cur.ua, cur.uh, t, cmid);
     } else if ((t & 127) < 72) {
       mc = stage_chroma<HST>(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
@@ -1386,7 +1512,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     const bool more = tile + 1 < tend;   // block-uniform
     if (more) {
       tile_next(F, geo);
-      cur = tile_load<SEMI>(F, geo, t, lofs);  // in flight during this tile's compute
+      cur = tile_load<SEMI, SUB>(F, geo, t, lofs);  // in flight during this tile's compute
     }
     __syncthreads();
     const bool fb = __builtin_amdgcn_readfirstlane(tflag[par]) == 0 && !F.chr444;
@@ -1452,12 +1578,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 // branch), explicitly instantiated in exactly one .hip each: the two chains'
 // product instances compile in their own translation units, so each gets the
 // scheduler that measured fastest for it (_build.py SOURCE_FLAGS)
-template <int DBG, int LPI, bool SEMI = false>
+template <int DBG, int LPI, bool SEMI = false, int SUB = 0>
 hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 grid, size_t lds, hipStream_t s) {
 #define X(T, M, D, L)                                                                       \
   if constexpr (L == LPI) {                                                                 \
     if (trc == T && tm == M && desat == D) {                                                \
-      hipLaunchKernelGGL((k_tile<T, M, D, L, DBG, SEMI>), grid, dim3(256), lds, s, F);      \
+      hipLaunchKernelGGL((k_tile<T, M, D, L, DBG, SEMI, SUB>), grid, dim3(256), lds, s, F); \
       return hipGetLastError();                                                             \
     }                                                                                       \
   }
@@ -1470,5 +1596,12 @@ hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 gri
   extern template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 #define H2S_TILE_INSTANCE(D, L, S) \
   template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+
+// the 4:2:2 / 4:4:4 input instances (SUB 1 / 2): the CPU chain's product
+// kernels with the output side's layout branches, one translation unit per SUB
+#define H2S_TILE_SUB_EXTERN(SUB) \
+  extern template hipError_t launch_tile<0, 0, true, SUB>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+#define H2S_TILE_SUB_INSTANCE(SUB) \
+  template hipError_t launch_tile<0, 0, true, SUB>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 
 }  // namespace h2s

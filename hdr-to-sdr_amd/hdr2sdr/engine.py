@@ -34,6 +34,7 @@ class Tonemapper:
         self.params: 'TonemapParams | None' = None
         self.lut_size = 0
         self._layouts = ('planar', 'planar')   # what the context last got (h2s_set_frame_layout)
+        self._subsampling = '420'              # ... (h2s_set_input_subsampling)
         if params is not None:
             self.set_params(params)
         if lut is not None:
@@ -106,10 +107,24 @@ class Tonemapper:
             self._check(self._L.h2s_set_frame_layout(self._ctx, _abi.LAYOUTS[in_layout], _abi.LAYOUTS[out_layout]))
             self._layouts = (in_layout, out_layout)
 
+    def set_input_subsampling(self, subsampling: str = '420') -> None:
+        """The chroma subsampling later calls read their source batch with
+        ('420' | '422' | '444'; h2s_set_input_subsampling).  process,
+        query_path, debug_float and peak_stats set it from their source
+        batch's ``subsampling``, so callers of those never need to."""
+        if subsampling not in _abi.SUBSAMPLINGS:
+            raise ValueError(f"subsampling must be '420', '422' or '444', got {subsampling!r}")
+        if subsampling != self._subsampling:
+            self._check(self._L.h2s_set_input_subsampling(self._ctx, _abi.SUBSAMPLINGS[subsampling]))
+            self._subsampling = subsampling
+
     def _use_layouts(self, src: FrameBatch, dst: 'FrameBatch | None' = None) -> None:
         # (a call without a destination batch leaves the output side as it is)
         self.set_frame_layout(getattr(src, 'layout', 'planar'),
                               self._layouts[1] if dst is None else getattr(dst, 'layout', 'planar'))
+        self.set_input_subsampling(getattr(src, 'subsampling', '420'))
+        if dst is not None and getattr(dst, 'subsampling', '420') != '420':
+            raise ValueError('the output side is 4:2:0 (destination batch subsampling must be 420)')
 
     @staticmethod
     def _stream_ptr(stream: Any) -> 'int | None':

@@ -19,6 +19,12 @@ interleaved (Cb, Cr) pairs (H/2 rows of W samples), the same number of bytes;
 10/12-bit samples carry the value in the high bits of their 16-bit word.  The
 kernels read and write both layouts in place (h2s_set_frame_layout);
 ``to_layout`` is the host-side repack for tests and callers.
+
+Source batches may also be planar 4:2:2 or 4:4:4 (``subsampling='422'`` /
+``'444'``: yuv422p10le / yuv444p10le and their 12-bit forms), with U and V
+planes of H x W/2 or H x W samples: W * H * 2 or W * H * 3 samples per frame.
+The kernels read them at their own chroma resolution
+(h2s_set_input_subsampling); the output side is always 4:2:0.
 """
 from __future__ import annotations
 
@@ -32,14 +38,23 @@ from . import _abi
 
 
 LAYOUTS = ('planar', 'semi')
+SUBSAMPLINGS = ('420', '422', '444')
+# chroma plane = (width >> cxs) x (height >> cys) samples
+_CHROMA_SHIFTS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}
 
 
 def sample_bytes(bits: int) -> int:
     return 1 if bits == 8 else 2
 
 
-def frame_bytes(width: int, height: int, bits: int) -> int:
-    return width * height * sample_bytes(bits) * 3 // 2
+def frame_samples(width: int, height: int, subsampling: str = '420') -> int:
+    """Samples of one frame: W * H * {3/2, 2, 3}."""
+    cxs, cys = _CHROMA_SHIFTS[subsampling]
+    return width * height + 2 * ((width >> cxs) * (height >> cys))
+
+
+def frame_bytes(width: int, height: int, bits: int, subsampling: str = '420') -> int:
+    return frame_samples(width, height, subsampling) * sample_bytes(bits)
 
 
 @dataclass
@@ -54,37 +69,46 @@ class FrameBatch:
     height: int
     bits: int
     layout: str = 'planar'
+    subsampling: str = '420'
 
     def __post_init__(self):
         if self.layout not in LAYOUTS:
             raise ValueError(f"layout must be 'planar' or 'semi', got {self.layout!r}")
+        if self.subsampling not in SUBSAMPLINGS:
+            raise ValueError(f"subsampling must be '420', '422' or '444', got {self.subsampling!r}")
+        if self.subsampling != '420' and self.layout == 'semi':
+            raise ValueError('4:2:2 / 4:4:4 batches are planar only (no p210 / p410)')
 
     # ---- constructors ---------------------------------------------------
     @staticmethod
-    def _shape(nframes: int, width: int, height: int, bits: int) -> 'tuple[int, int]':
+    def _shape(nframes: int, width: int, height: int, bits: int, subsampling: str = '420') -> 'tuple[int, int]':
+        # (4:2:2 / 4:4:4 sources too: the output they convert to is 4:2:0)
         if width <= 0 or height <= 0 or width % 2 or height % 2:
             raise ValueError(f'4:2:0 frames need positive even dimensions, got {width}x{height}')
         if bits not in (8, 10, 12):
             raise ValueError(f'bits must be 8, 10 or 12, got {bits}')
-        return nframes, width * height * 3 // 2
+        if subsampling not in SUBSAMPLINGS:
+            raise ValueError(f"subsampling must be '420', '422' or '444', got {subsampling!r}")
+        return nframes, frame_samples(width, height, subsampling)
 
     @classmethod
     def empty_torch(cls, nframes: int, width: int, height: int, bits: int, device: Any,
-                    layout: str = 'planar') -> 'FrameBatch':
+                    layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
         import torch
         dt = torch.uint8 if bits == 8 else torch.int16
-        return cls(torch.empty(cls._shape(nframes, width, height, bits), dtype=dt, device=device),
-                   width, height, bits, layout)
+        return cls(torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, device=device),
+                   width, height, bits, layout, subsampling)
 
     @classmethod
     def empty_numpy(cls, nframes: int, width: int, height: int, bits: int,
-                    layout: str = 'planar') -> 'FrameBatch':
+                    layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
         dt = np.uint8 if bits == 8 else np.uint16
-        return cls(np.zeros(cls._shape(nframes, width, height, bits), dtype=dt), width, height, bits, layout)
+        return cls(np.zeros(cls._shape(nframes, width, height, bits, subsampling), dtype=dt), width, height, bits,
+                   layout, subsampling)
 
     @classmethod
     def empty_pinned(cls, nframes: int, width: int, height: int, bits: int,
-                     layout: str = 'planar') -> 'FrameBatch':
+                     layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
         """Host batch in page-locked memory (DMA-able without a bounce copy:
         the host-buffer path of h2s_process then runs at PCIe speed). Falls
         back to pageable numpy memory when no GPU runtime is present."""
@@ -92,20 +116,22 @@ class FrameBatch:
             import torch
             if torch.cuda.is_available():
                 dt = torch.uint8 if bits == 8 else torch.int16
-                t = torch.empty(cls._shape(nframes, width, height, bits), dtype=dt, pin_memory=True)
+                t = torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, pin_memory=True)
                 a = t.numpy() if bits == 8 else t.numpy().view(np.uint16)
-                fb = cls(a, width, height, bits, layout)
+                fb = cls(a, width, height, bits, layout, subsampling)
                 fb._pin = t          # keep the pinned allocation alive
                 return fb
         except (ImportError, RuntimeError):
             pass
-        return cls.empty_numpy(nframes, width, height, bits, layout)
+        return cls.empty_numpy(nframes, width, height, bits, layout, subsampling)
 
     @classmethod
-    def from_planes(cls, y: np.ndarray, u: np.ndarray, v: np.ndarray, bits: int) -> 'FrameBatch':
-        """Pack [F,H,W] / [F,H/2,W/2] numpy planes into a batch."""
+    def from_planes(cls, y: np.ndarray, u: np.ndarray, v: np.ndarray, bits: int,
+                    subsampling: str = '420') -> 'FrameBatch':
+        """Pack [F,H,W] / [F,H/2,W/2] numpy planes into a batch (4:2:2: U, V
+        [F,H,W/2]; 4:4:4: [F,H,W])."""
         f, h, w = y.shape
-        fb = cls.empty_numpy(f, w, h, bits)
+        fb = cls.empty_numpy(f, w, h, bits, 'planar', subsampling)
         fb.y[...] = y
         fb.u[...] = u
         fb.v[...] = v
@@ -123,13 +149,14 @@ class FrameBatch:
     def _plane(self, p: int):
         w, h = self.width, self.height
         ysz = w * h
-        csz = ysz // 4
+        cxs, cys = _CHROMA_SHIFTS[self.subsampling]
+        csz = (w >> cxs) * (h >> cys)
         if p == 0:
             return self.buf[:, :ysz].reshape(self.nframes, h, w)
         if self.layout == 'semi':
             return self.uv[..., p - 1]
         off = ysz + (p - 1) * csz
-        return self.buf[:, off:off + csz].reshape(self.nframes, h // 2, w // 2)
+        return self.buf[:, off:off + csz].reshape(self.nframes, h >> cys, w >> cxs)
 
     @property
     def uv(self):
@@ -158,18 +185,18 @@ class FrameBatch:
         a = self.buf.detach().cpu().numpy()
         if self.bits != 8:
             a = a.view(np.uint16)
-        return FrameBatch(a, self.width, self.height, self.bits, self.layout)
+        return FrameBatch(a, self.width, self.height, self.bits, self.layout, self.subsampling)
 
     def to_torch(self, device: Any) -> 'FrameBatch':
         import torch
         if self.is_torch:
-            return FrameBatch(self.buf.to(device), self.width, self.height, self.bits, self.layout)
+            return FrameBatch(self.buf.to(device), self.width, self.height, self.bits, self.layout, self.subsampling)
         a = self.buf if self.bits == 8 else self.buf.view(np.int16)
         return FrameBatch(torch.from_numpy(np.ascontiguousarray(a)).to(device), self.width, self.height, self.bits,
-                          self.layout)
+                          self.layout, self.subsampling)
 
     def slice(self, start: int, stop: int) -> 'FrameBatch':
-        return FrameBatch(self.buf[start:stop], self.width, self.height, self.bits, self.layout)
+        return FrameBatch(self.buf[start:stop], self.width, self.height, self.bits, self.layout, self.subsampling)
 
     def to_layout(self, layout: str) -> 'FrameBatch':
         """A copy of the batch in ``layout`` (the batch itself when it already
@@ -180,6 +207,8 @@ class FrameBatch:
         in place and never calls it."""
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be 'planar' or 'semi', got {layout!r}")
+        if self.subsampling != '420':
+            raise ValueError('to_layout repacks 4:2:0 batches only (4:2:2 / 4:4:4 batches are planar)')
         if layout == self.layout:
             return self
         sh = 0 if self.bits == 8 else 16 - self.bits
@@ -229,7 +258,8 @@ class FrameBatch:
             base = self.buf.ctypes.data
             loc = _abi.LOC_HOST
         ysz = w * h * sb
-        csz = ysz // 4
+        cxs, cys = _CHROMA_SHIFTS[self.subsampling]
+        csz = (w >> cxs) * (h >> cys) * sb
         fpitch = ysz + 2 * csz
         d.data[0] = base
         d.data[1] = base + ysz
@@ -240,7 +270,7 @@ class FrameBatch:
             d.frame_pitch[0] = d.frame_pitch[1] = fpitch
         else:
             d.data[2] = base + ysz + csz
-            d.linesize[1] = d.linesize[2] = (w // 2) * sb
+            d.linesize[1] = d.linesize[2] = (w >> cxs) * sb
             for p in range(3):
                 d.frame_pitch[p] = fpitch
         d.width, d.height, d.bits, d.location = w, h, self.bits, loc

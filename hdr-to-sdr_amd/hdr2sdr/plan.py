@@ -10,7 +10,9 @@ encode and mux. The tone-map chain moves onto the GPU between two pipes:
 
     decode:  ffmpeg -i IN -map 0:v:0 -f rawvideo -pix_fmt yuv420p1Xle -
              (or p010le / p012le, and nv12 / p010le / p012le on the encode
-             pipe: the semi-planar layouts, ``in_layout`` / ``out_layout``)
+             pipe: the semi-planar layouts, ``in_layout`` / ``out_layout``;
+             or yuv422p1Xle / yuv444p1Xle for such a source on the CPU chain,
+             ``in_subsampling``)
     libh2s:  h2s_process() on batches of frames
     encode:  ffmpeg -f rawvideo … -i - -i IN <every non-filter option build() chose>
 
@@ -38,6 +40,10 @@ from .chain import DOVI_P5_ERROR, TonemapParams, is_dovi_profile5, parse_filter_
 PIPE_PIX_FMT = {8: 'yuv420p', 10: 'yuv420p10le', 12: 'yuv420p12le'}
 # the semi-planar formats (hardware decoder / encoder surfaces), by bit depth
 PIPE_PIX_FMT_SEMI = {8: 'nv12', 10: 'p010le', 12: 'p012le'}
+# planar 4:2:2 / 4:4:4 sources the decode pipe can carry as they are (CPU chain)
+PIPE_PIX_FMT_SUB = {'422': {10: 'yuv422p10le', 12: 'yuv422p12le'}, '444': {10: 'yuv444p10le', 12: 'yuv444p12le'}}
+# ffprobe pix_fmt -> in_subsampling='auto'
+SOURCE_SUBSAMPLING = {'yuv422p10le': '422', 'yuv422p12le': '422', 'yuv444p10le': '444', 'yuv444p12le': '444'}
 # encoder -pix_fmt values build() emits (src/ffmpeg_command.py:355-368) -> bits
 OUT_PIX_FMT_BITS = {'yuv420p': 8, 'yuv420p10le': 10, 'p010le': 10, 'yuv420p12le': 12}
 # setparams=color_primaries=bt709:color_trc=bt709:colorspace=bt709 (src/utils.py:40)
@@ -61,10 +67,13 @@ class PipePlan:
     # emits and what the encode side is fed
     in_layout: str = 'planar'
     layout: str = 'planar'
+    # chroma subsampling on the decode pipe ('420' | '422' | '444')
+    in_subsampling: str = '420'
 
     @property
     def frame_bytes_in(self) -> int:
-        return self.width * self.height * 3 // 2 * (1 if self.params.bits_in == 8 else 2)
+        from .frames import frame_bytes
+        return frame_bytes(self.width, self.height, self.params.bits_in, self.in_subsampling)
 
     @property
     def frame_bytes_out(self) -> int:
@@ -79,7 +88,8 @@ def _remap_input(spec: str) -> str:
 
 
 def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[str, Any] | None' = None,
-                   mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar') -> PipePlan:
+                   mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar',
+                   in_subsampling: str = '420') -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
 
     in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
@@ -89,6 +99,19 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     src/ffmpeg_command.py:365-368): the encoder then takes the pipe's frames
     as they are instead of repacking each one on the CPU.  in_layout='auto'
     is planar (a software decoder's native output).
+
+    in_subsampling ('420' | '422' | '444' | 'auto'): the chroma subsampling on
+    the decode pipe.  With '422' / '444' a CPU-chain plan asks the decoder for
+    yuv422p1Xle / yuv444p1Xle, so a ProRes 422 / 4444 or HEVC 4:2:2 / 4:4:4
+    source reaches the kernels at its own chroma resolution, as it reaches
+    zscale in the reference's chain (no swscale chroma pass in front).
+    'auto' reads ``properties.get('pix_fmt')`` (ffprobe's stream field; the
+    reference's ``get_video_properties`` dict does not carry it, and without
+    it the answer is '420'): yuv422p10le / 12le and yuv444p10le / 12le map to
+    themselves, anything else is '420'.  A libplacebo chain always pipes 4:2:0
+    whatever is asked: the reference uploads ``format=p010`` there
+    (src/utils.py:430-431), so swscale's 4:2:0 is what libplacebo sees.
+    Planar input only.
 
     properties: the reference's ``get_video_properties`` dict
     (src/utils.py:1040-1058): width, height, bit_depth, color_transfer.
@@ -159,9 +182,19 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
             raise ValueError(f"layout must be 'planar', 'semi' or 'auto', got {name!r}")
     if in_layout == 'auto':
         in_layout = 'planar'
+    if in_subsampling not in ('420', '422', '444', 'auto'):
+        raise ValueError(f"in_subsampling must be '420', '422', '444' or 'auto', got {in_subsampling!r}")
+    if in_subsampling == 'auto':
+        in_subsampling = SOURCE_SUBSAMPLING.get(str(properties.get('pix_fmt') or ''), '420')
+    if params.resolved_pipeline() == 'libplacebo':
+        in_subsampling = '420'     # format=p010,hwupload: the reference's own 4:2:0
+    if in_subsampling != '420' and in_layout == 'semi':
+        raise ValueError('4:2:2 / 4:4:4 decode pipes are planar only (no p210 / p410)')
     if out_layout == 'auto':
         out_layout = 'semi' if enc_pix_fmt == 'p010le' else 'planar'
     pipe_in = (PIPE_PIX_FMT_SEMI if in_layout == 'semi' else PIPE_PIX_FMT)[bits_in]
+    if in_subsampling != '420':
+        pipe_in = PIPE_PIX_FMT_SUB[in_subsampling][bits_in]
     pipe_out = (PIPE_PIX_FMT_SEMI if out_layout == 'semi' else PIPE_PIX_FMT)[bits_out]
     decode = [exe, '-loglevel', 'error', '-nostdin', '-i', input_path, '-map', '0:v:0',
               '-f', 'rawvideo', '-pix_fmt', pipe_in, '-']
@@ -169,7 +202,7 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
               '-r', fps, '-i', '-', '-i', input_path, '-map', '0:v:0'] + encode_opts
     return PipePlan(decode=decode, encode=encode, params=params, lut_path=lut_path, width=W, height=H,
                     input_path=input_path, output_path=output_path, reference_argv=argv,
-                    in_layout=in_layout, layout=out_layout)
+                    in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -206,7 +239,8 @@ class H2SProcess:
         # page-locked staging: the pipe bytes go straight to / from HBM by DMA.
         # `depth` input slots let the decoder run ahead while the GPU stage
         # and the encoder work on earlier batches.
-        self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout)
+        self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout,
+                                             plan.in_subsampling)
                      for _ in range(max(1, int(depth)))]
         self._dst = FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_out, plan.layout)
         self._free: 'queue.Queue[Optional[int]]' = queue.Queue()

@@ -60,7 +60,8 @@ extern "C" {
  *      fails loudly instead of switching kernels); the libplacebo branch's
  *      exact path computes stages 1-3 in double precision (see below).
  * Added within 3.4, with no change of either number: h2s_set_frame_layout
- * (semi-planar nv12 / p010le / p012le frame sets).  No struct, signature or
+ * (semi-planar nv12 / p010le / p012le frame sets); h2s_set_input_subsampling
+ * (4:2:2 / 4:4:4 planar input on the CPU chain).  No struct, signature or
  * default behaviour changes, so the symbol's presence in the loaded library
  * is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -123,6 +124,10 @@ enum h2s_location { H2S_LOC_DEVICE = 0, H2S_LOC_HOST = 1 };
  * samples with the code in the high bits (nv12 / p010le / p012le: what
  * hardware decoders produce and hardware encoders take). */
 enum h2s_layout { H2S_LAYOUT_PLANAR = 0, H2S_LAYOUT_SEMI = 1 };
+
+/* Chroma subsampling of an input frame set (h2s_set_input_subsampling).  The
+ * output side is always 4:2:0. */
+enum h2s_subsampling { H2S_SUB_420 = 0, H2S_SUB_422 = 1, H2S_SUB_444 = 2 };
 
 /* Debug stages for h2s_debug_float: three float planes per pixel.
  * 1..4: R, G, B after the stage.  5: the quantiser's inputs, before rounding:
@@ -342,6 +347,15 @@ typedef struct h2s_frames {
  * frame_pitch.  Row starts that are 16-byte aligned (8 for nv12) run on the
  * tile kernel, others on the generic one (h2s_query_path), as for planar. */
 
+/* An input set of another chroma subsampling (h2s_set_input_subsampling;
+ * planar only, codes in the low bits, bits 10 or 12) has chroma planes 1, 2 of
+ *   H2S_SUB_422 (yuv422p10le / 12le): width/2 samples x height rows,
+ *     linesize[1, 2] >= width/2 * 2 bytes;
+ *   H2S_SUB_444 (yuv444p10le / 12le): width samples x height rows,
+ *     linesize[1, 2] >= width * 2 bytes.
+ * Width and height are still even: the output is 4:2:0.  A tight frame is
+ * width * height * {3/2, 2, 3} samples. */
+
 typedef struct h2s_ctx h2s_ctx;
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -388,7 +402,9 @@ int h2s_process(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out,
  * generic one).  With peak_detect the curve uses the static peak (the
  * parameters' resolved peak), not the context's smoothed state: the debug
  * planes are a per-frame check of the arithmetic and leave that state
- * untouched.  Synchronous. */
+ * untouched.  With 4:2:2 / 4:4:4 input (h2s_set_input_subsampling) the planes
+ * are the generic kernel's whatever h2s_query_path says: the tile kernel has
+ * no debug instances for those inputs.  Synchronous. */
 int h2s_debug_float(h2s_ctx *ctx, const h2s_frames *in, int stage,
                     float *out_rgb, int out_location, void *hip_stream);
 
@@ -409,6 +425,27 @@ int h2s_query_path(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out);
  * launches change, so the call does not wait for queued work.  An unknown
  * value or a NULL ctx is H2S_E_INVALID_ARG. */
 int h2s_set_frame_layout(h2s_ctx *ctx, int in_layout, int out_layout);
+
+/* ---- input chroma subsampling (enum h2s_subsampling; default 420) --------
+ * How every later call on the context reads the chroma planes of its `in`
+ * frames: h2s_process (device and host-resident sets), h2s_query_path,
+ * h2s_debug_float and h2s_preview_rgb24 / _batch.  The conversion kernels read
+ * a 4:2:2 / 4:4:4 source at its own chroma resolution, as the reference's CPU
+ * chain does (zscale takes what the decoder produced), instead of a 4:2:0
+ * frame that swscale decimated first.  Model ([EXT], unpinned like the rest of
+ * S1): 4:2:2 chroma is co-sited with the even luma column and
+ * lines up with every luma row, so S1 is the horizontal pass alone on chroma
+ * row y (C[2k] = c[k], C[2k+1] = c[k]/2 + c[k+1]/2, column width/2 by
+ * params.chroma_edge); 4:4:4 is not resampled.  Everything after S1, and the
+ * 4:2:0 output, is unchanged.  Only the arguments of later launches change, so
+ * the call does not wait for queued work.  An unknown value or a NULL ctx is
+ * H2S_E_INVALID_ARG.  With 422 / 444 set, each of these is H2S_E_UNSUPPORTED
+ * (h2s_last_error says why), never another route:
+ *   - H2S_LAYOUT_SEMI on the input side (p210 / p410);
+ *   - the libplacebo pipeline (params resolve to H2S_PIPE_LIBPLACEBO, hence
+ *     peak_detect too): the reference uploads format=p010 there, i.e. 4:2:0;
+ *   - h2s_peak_stats. */
+int h2s_set_input_subsampling(h2s_ctx *ctx, int subsampling);
 
 /* ---- dynamic peak (params.peak_detect, BT.2390 / spline) -----------------
  * h2s_peak_reset: forget the smoothing state (a new sequence / scene cut).
