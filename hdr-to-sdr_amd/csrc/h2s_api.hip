@@ -51,6 +51,30 @@ constexpr int kMaxChunks = 8;  // host-frame pipeline depth (chunks per call)
 int fail(h2s_ctx* c, int code, const std::string& msg);
 int hip_fail(h2s_ctx* c, hipError_t e, const char* what);
 
+// The form of a frame set: its layout (enum h2s_layout; semi-planar: plane 1
+// holds (Cb, Cr) pairs, a row of it is as long as a luma row, plane 2 is
+// unused) and its chroma subsampling (enum h2s_subsampling: chroma planes of
+// width >> cxs samples x height >> cys rows; a semi-planar set and every
+// output set is 4:2:0).  Whatever reads an h2s_frames takes its Format, never
+// defaulted; the planes' sizes are written here and nowhere else
+struct Format {
+  int layout, sub;
+  bool semi() const { return layout == H2S_LAYOUT_SEMI; }
+  int cxs() const { return sub == H2S_SUB_444 ? 0 : 1; }
+  int cys() const { return sub == H2S_SUB_420 ? 1 : 0; }
+  int planes() const { return semi() ? 2 : 3; }
+  struct Plane {
+    long long row_bytes, rows;
+  };
+  Plane plane(const h2s_frames* f, int p) const {
+    const long long bps = f->bits == 8 ? 1 : 2;
+    if (p == 0) return {f->width * bps, f->height};
+    // (semi-planar: pairs, so a 4:2:0 row is as long as a luma row)
+    return {(f->width >> cxs()) * bps * (semi() ? 2 : 1), f->height >> cys()};
+  }
+};
+constexpr Format PLANAR_420{H2S_LAYOUT_PLANAR, H2S_SUB_420};
+
 // ---- owners of the context's device resources ----
 
 // device buffer of at least `cap` bytes (grown, never shrunk); a grown
@@ -181,10 +205,9 @@ struct __attribute__((visibility("hidden"))) h2s_ctx {
   Ordered lut_built;      // after the last build of d_lut_yuv / d_lut8x (queued on the caller's stream)
   bool fast_enabled = true;
   bool lp_exact = false;  // H2S_OPT_LP_EXACT
-  // h2s_set_frame_layout: how later calls read `in` and write `out` (enum h2s_layout)
-  int in_layout = H2S_LAYOUT_PLANAR, out_layout = H2S_LAYOUT_PLANAR;
-  // h2s_set_input_subsampling: the chroma subsampling later calls read `in` with (enum h2s_subsampling)
-  int in_sub = H2S_SUB_420;
+  // how later calls read `in` and write `out`: h2s_set_frame_layout sets both
+  // layouts, h2s_set_input_subsampling in_fmt.sub (the output is always 4:2:0)
+  Format in_fmt = PLANAR_420, out_fmt = PLANAR_420;
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
@@ -608,142 +631,119 @@ void build_hlg_table(std::vector<float4>* out) {
 
 bool aligned(const void* p, long long a) { return ((uintptr_t)p % (uintptr_t)a) == 0; }
 
-// semi (here and below): the set's layout (enum h2s_layout, never defaulted);
-// semi-planar (H2S_LAYOUT_SEMI): plane 1 holds (Cb, Cr) pairs, a row of it is
-// as long as a luma row, plane 2 is unused
-// sub (here and below): an input set's chroma subsampling (enum
-// h2s_subsampling; output sets are 4:2:0): chroma planes of width >> cxs
-// samples x height >> cys rows
-int sub_cxs(int sub) { return sub == H2S_SUB_444 ? 0 : 1; }
-int sub_cys(int sub) { return sub == H2S_SUB_420 ? 1 : 0; }
-
-int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, int semi, int sub = H2S_SUB_420) {
+int check_frames(h2s_ctx* c, const h2s_frames* f, int bits, const char* which, Format fmt) {
   if (!f) return fail(c, H2S_E_INVALID_ARG, std::string(which) + " frames is NULL");
   if (f->width <= 0 || f->height <= 0) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": empty frame");
   if ((f->width & 1) || (f->height & 1))
-    return fail(c, H2S_E_UNSUPPORTED, std::string(which) + (sub ? ": the 4:2:0 output needs even width and height"
-                                                                 : ": 4:2:0 frames need even width and height"));
+    return fail(c, H2S_E_UNSUPPORTED, std::string(which) + (fmt.sub ? ": the 4:2:0 output needs even width and height"
+                                                                     : ": 4:2:0 frames need even width and height"));
   if (f->bits != bits)
     return fail(c, H2S_E_INVALID_ARG,
                 std::string(which) + ": bits " + std::to_string(f->bits) + " != params " + std::to_string(bits));
   if (f->location != H2S_LOC_DEVICE && f->location != H2S_LOC_HOST)
     return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": bad location");
   const int bps = bits == 8 ? 1 : 2;
-  const long long crow = (long long)(f->width >> sub_cxs(sub)) * bps * (semi ? 2 : 1);
-  const long long rowb[3] = {(long long)f->width * bps, crow, crow};
-  for (int p = 0; p < (semi ? 2 : 3); p++) {
+  for (int p = 0; p < fmt.planes(); p++) {
     if (!f->data[p]) return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": NULL plane");
-    if (f->linesize[p] < rowb[p])
+    if (f->linesize[p] < fmt.plane(f, p).row_bytes)
       return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": linesize smaller than a row");
     if (bps == 2 && ((f->linesize[p] & 1) || !aligned(f->data[p], 2)))
       return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": 16-bit planes must be 2-byte aligned");
-    if (semi && bps == 2 && (f->frame_pitch[p] & 1))
+    if (fmt.semi() && bps == 2 && (f->frame_pitch[p] & 1))
       return fail(c, H2S_E_INVALID_ARG, std::string(which) + ": 16-bit planes need an even frame pitch");
   }
   return 0;
 }
 
-// vector path needs 16-B luma / 8-B chroma alignment of every row start
-// (semi-planar: four pairs of the interleaved plane are one luma-sized access)
-// (4:4:4 input: a chroma row is read like a luma row)
-bool vec_ok(const h2s_frames* f, bool out8, int semi, int sub = H2S_SUB_420) {
-  const long long ay = out8 ? 8 : 16, ac = semi || sub == H2S_SUB_444 ? ay : (out8 ? 4 : 8);
-  const long long a[3] = {ay, ac, ac};
-  for (int p = 0; p < (semi ? 2 : 3); p++)
-    if (!aligned(f->data[p], a[p]) || f->linesize[p] % a[p] || f->frame_pitch[p] % a[p]) return false;
-  return true;
-}
-
-// tile kernel: at least one 64-pixel tile, every row start 16-B aligned (8-B
-// for 8-bit chroma output)
-// (semi-planar: the same for the two planes it has)
-bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, int in_semi, int out_semi) {
-  if (in->width < tw) return false;  // width % tw columns go to k_process (launch_columns)
-  for (int p = 0; p < 3; p++) {
-    if (!(in_semi && p == 2) &&
-        (!aligned(in->data[p], 16) || in->linesize[p] % 16 || in->frame_pitch[p] % 16))
-      return false;
-    const long long a = out8 ? 8 : 16;
-    if (!(out_semi && p == 2) &&
-        (!aligned(out->data[p], a) || out->linesize[p] % a || out->frame_pitch[p] % a))
-      return false;
+// every plane fmt has: its base, its rows and its frames a bytes apart
+bool planes_aligned(const h2s_frames* f, Format fmt, long long ay, long long ac) {
+  for (int p = 0; p < fmt.planes(); p++) {
+    const long long a = p ? ac : ay;
+    if (!aligned(f->data[p], a) || f->linesize[p] % a || f->frame_pitch[p] % a) return false;
   }
   return true;
 }
 
-size_t frame_bytes(const h2s_frames* f, int sub = H2S_SUB_420) {
-  const size_t bps = f->bits == 8 ? 1 : 2, ysz = (size_t)f->width * f->height * bps;
-  return ysz + 2 * (ysz >> (sub_cxs(sub) + sub_cys(sub)));
+// vector path needs 16-B luma / 8-B chroma alignment of every row start
+// (semi-planar: four pairs of the interleaved plane are one luma-sized access)
+// (4:4:4 input: a chroma row is read like a luma row)
+bool vec_ok(const h2s_frames* f, bool out8, Format fmt) {
+  const long long ay = out8 ? 8 : 16;
+  return planes_aligned(f, fmt, ay, fmt.semi() || fmt.sub == H2S_SUB_444 ? ay : ay / 2);
 }
 
-// tight device copy descriptor laid out in `base`
-// (semi-planar: the interleaved plane takes the two chroma planes' place,
-// so a frame's bytes are the same)
-h2s_frames tight(const h2s_frames* f, void* base, int semi, int sub = H2S_SUB_420) {
+// tile kernel: at least one 64-pixel tile, every row start 16-B aligned (8-B
+// for 8-bit output), of the planes each set has
+bool tile_ok(const h2s_frames* in, const h2s_frames* out, bool out8, int tw, Format in_fmt, Format out_fmt) {
+  if (in->width < tw) return false;  // width % tw columns go to k_process (launch_columns)
+  const long long a = out8 ? 8 : 16;
+  return planes_aligned(in, in_fmt, 16, 16) && planes_aligned(out, out_fmt, a, a);
+}
+
+size_t frame_bytes(const h2s_frames* f, Format fmt) {
+  size_t n = 0;
+  for (int p = 0; p < fmt.planes(); p++) n += (size_t)(fmt.plane(f, p).row_bytes * fmt.plane(f, p).rows);
+  return n;
+}
+
+// tight device copy descriptor laid out in `base`: the planes fmt has back to
+// back, rows packed, frames frame_bytes apart (a semi-planar frame's bytes
+// are the planar one's); a plane it has not is zero
+h2s_frames tight(const h2s_frames* f, void* base, Format fmt) {
   h2s_frames t = *f;
-  const long long bps = f->bits == 8 ? 1 : 2;
-  const long long ysz = (long long)f->width * f->height * bps, csz = ysz >> (sub_cxs(sub) + sub_cys(sub));
-  const long long fb = ysz + 2 * csz;
-  t.data[0] = base;
-  t.data[1] = (uint8_t*)base + ysz;
-  t.data[2] = (uint8_t*)base + ysz + csz;
-  t.linesize[0] = f->width * bps;
-  t.linesize[1] = t.linesize[2] = (f->width >> sub_cxs(sub)) * bps;
-  t.frame_pitch[0] = t.frame_pitch[1] = t.frame_pitch[2] = fb;
-  if (semi) t.data[2] = nullptr, t.linesize[1] = f->width * bps, t.linesize[2] = 0, t.frame_pitch[2] = 0;
+  const long long fb = (long long)frame_bytes(f, fmt);
+  long long off = 0;
+  for (int p = 0; p < 3; p++) {
+    const bool has = p < fmt.planes();
+    t.data[p] = has ? (uint8_t*)base + off : nullptr;
+    t.linesize[p] = has ? fmt.plane(f, p).row_bytes : 0;
+    t.frame_pitch[p] = has ? fb : 0;
+    if (has) off += fmt.plane(f, p).row_bytes * fmt.plane(f, p).rows;
+  }
   t.location = H2S_LOC_DEVICE;
   return t;
 }
 
 // the set the kernels bind: a device set itself, a host set's tight copy staged in `base`
-h2s_frames device_view(const h2s_frames* f, void* base, int semi, int sub = H2S_SUB_420) {
-  return f->location == H2S_LOC_HOST ? tight(f, base, semi, sub) : *f;
+h2s_frames device_view(const h2s_frames* f, void* base, Format fmt) {
+  return f->location == H2S_LOC_HOST ? tight(f, base, fmt) : *f;
 }
 
 // the whole batch is one contiguous span laid out as tight() describes
-bool is_tight(const h2s_frames* f, int semi, int sub = H2S_SUB_420) {
-  const long long bps = f->bits == 8 ? 1 : 2;
-  const long long ysz = (long long)f->width * f->height * bps, csz = ysz >> (sub_cxs(sub) + sub_cys(sub)), fb = ysz + 2 * csz;
-  const long long cls = (f->width >> sub_cxs(sub)) * bps;
-  if (semi)
-    return f->linesize[0] == f->width * bps && f->linesize[1] == f->width * bps && f->frame_pitch[0] == fb &&
-           f->frame_pitch[1] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz;
-  return f->linesize[0] == f->width * bps && f->linesize[1] == cls &&
-         f->linesize[2] == cls && f->frame_pitch[0] == fb && f->frame_pitch[1] == fb &&
-         f->frame_pitch[2] == fb && (const uint8_t*)f->data[1] == (const uint8_t*)f->data[0] + ysz &&
-         (const uint8_t*)f->data[2] == (const uint8_t*)f->data[1] + csz;
+bool is_tight(const h2s_frames* f, Format fmt) {
+  const h2s_frames t = tight(f, f->data[0], fmt);
+  for (int p = 0; p < fmt.planes(); p++)
+    if (f->data[p] != t.data[p] || f->linesize[p] != t.linesize[p] || f->frame_pitch[p] != t.frame_pitch[p])
+      return false;
+  return true;
 }
 
-hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, int semi,
-                       int sub = H2S_SUB_420) {
-  const long long bps = src->bits == 8 ? 1 : 2;
-  if (is_tight(src, semi, sub) && is_tight(dst, semi, sub))  // one DMA for the whole batch
+hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes, hipStream_t s, Format fmt) {
+  if (is_tight(src, fmt) && is_tight(dst, fmt))  // one DMA for the whole batch
     return hipMemcpyAsync(dst->data[0], src->data[0], (size_t)src->frame_pitch[0] * nframes, hipMemcpyDefault, s);
   for (int fr = 0; fr < nframes; fr++)
-    for (int p = 0; p < (semi ? 2 : 3); p++) {
-      const long long w = (p && !semi ? src->width >> sub_cxs(sub) : src->width) * bps;
-      const long long h = p ? src->height >> sub_cys(sub) : src->height;
+    for (int p = 0; p < fmt.planes(); p++) {
+      const Format::Plane pl = fmt.plane(src, p);
       hipError_t e = hipMemcpy2DAsync((uint8_t*)dst->data[p] + fr * dst->frame_pitch[p], dst->linesize[p],
-                                      (const uint8_t*)src->data[p] + fr * src->frame_pitch[p], src->linesize[p], w,
-                                      h, hipMemcpyDefault, s);
+                                      (const uint8_t*)src->data[p] + fr * src->frame_pitch[p], src->linesize[p],
+                                      pl.row_bytes, pl.rows, hipMemcpyDefault, s);
       if (e != hipSuccess) return e;
     }
   return hipSuccess;
 }
 
-// in_semi / out_semi: the sets' layouts (h2s_set_frame_layout).  A semi-planar
-// set is bound with plane 2 as plane 1 one sample on, samples two apart, so
+// A semi-planar set (h2s_set_frame_layout) is bound with plane 2 as plane 1 one sample on, samples two apart, so
 // the kernels address both layouts alike; 16-bit words carry the code in
 // their high bits
-// in_sub: the input's chroma subsampling (h2s_set_input_subsampling): its
-// chroma plane is icw x ich; cw, ch, ngx and total stay the output's
-void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes, int in_semi,
-                   int out_semi, int in_sub = H2S_SUB_420) {
+// The input's chroma plane (h2s_set_input_subsampling) is icw x ich; cw, ch,
+// ngx and total stay the output's
+void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes, Format in_fmt,
+                   Format out_fmt) {
   k->W = in->width;
   k->H = in->height;
   k->cw = in->width / 2;
   k->ch = in->height / 2;
-  k->sub = in_sub, k->icw = in->width >> sub_cxs(in_sub), k->ich = in->height >> sub_cys(in_sub);
+  k->sub = in_fmt.sub, k->icw = in->width >> in_fmt.cxs(), k->ich = in->height >> in_fmt.cys();
   k->ngx = (k->cw + 3) / 4;
   k->nframes = nframes;
   k->total = (long long)nframes * k->ch * k->ngx;
@@ -758,12 +758,12 @@ void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int 
     }
   }
   k->in_cstep = k->out_cstep = 1, k->in_sh = k->out_sh = 0;
-  if (in_semi) {
+  if (in_fmt.semi()) {
     k->in[2] = k->in[1] + 2, k->in_ls[2] = k->in_ls[1], k->in_fp[2] = k->in_fp[1];
     k->in_cstep = 2, k->in_sh = 16 - in->bits;
     k->in_mask &= 0xFFFFu >> k->in_sh;
   }
-  if (out && out_semi) {
+  if (out && out_fmt.semi()) {
     const int bps = out->bits == 8 ? 1 : 2;
     k->out[2] = k->out[1] + bps, k->out_ls[2] = k->out_ls[1], k->out_fp[2] = k->out_fp[1];
     k->out_cstep = 2, k->out_sh = bps == 2 ? 16 - out->bits : 0;
@@ -1184,9 +1184,8 @@ static void chroma_taps(float* wx7, float* wy8) {
 struct Route {
   int path;                    // H2S_PATH_*
   bool vec, out8;
-  int in_layout, out_layout;   // enum h2s_layout
+  Format in_fmt, out_fmt;      // the two sets' forms
   hipStream_t s;
-  int in_sub = H2S_SUB_420;    // enum h2s_subsampling
   bool tile() const { return path == H2S_PATH_TILE || path == H2S_PATH_TILE_TAIL; }
   Route on(hipStream_t other) const {
     Route r = *this;
@@ -1323,18 +1322,18 @@ static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
 }
 
 static int choose_path(const h2s_ctx* c, const KParams& k, const h2s_frames* din, const h2s_frames* dout,
-                       bool out8) {
+                       bool out8, Format in_fmt, Format out_fmt) {
   const int tw = h2s::TBW;
-  if (fast_params_ok(c, k) && tile_ok(din, dout, out8, tw, k.in_cstep == 2, k.out_cstep == 2))
+  if (fast_params_ok(c, k) && tile_ok(din, dout, out8, tw, in_fmt, out_fmt))
     return (din->width & (tw - 1)) ? H2S_PATH_TILE_TAIL : H2S_PATH_TILE;
   return c->params.chroma_filter == H2S_CHROMA_BICUBIC ? H2S_PATH_TWO_PASS : H2S_PATH_GENERIC;
 }
 
 // what a 4:2:2 / 4:4:4 input set (h2s_set_input_subsampling) does not run
 // with: each is refused, none is routed to something else.  k: resolved
-static int check_subsampling(h2s_ctx* c, const KParams& k, int in_layout, int in_sub) {
-  if (in_sub == H2S_SUB_420) return 0;
-  if (in_layout == H2S_LAYOUT_SEMI)
+static int check_subsampling(h2s_ctx* c, const KParams& k, Format in_fmt) {
+  if (in_fmt.sub == H2S_SUB_420) return 0;
+  if (in_fmt.semi())
     return fail(c, H2S_E_UNSUPPORTED, "4:2:2 / 4:4:4 input is planar only (semi-planar p210 / p410 input is not supported)");
   if (k.pipe == h2s::PIPE_LIBPLACEBO)
     return fail(c, H2S_E_UNSUPPORTED,
@@ -1575,15 +1574,15 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   KParams k;
   int rc = prepare(c, &k, false);  // the statistics need no LUT
   if (rc) return rc;
-  if (c->in_sub != H2S_SUB_420)
+  if (c->in_fmt.sub != H2S_SUB_420)
     return fail(c, H2S_E_UNSUPPORTED, "h2s_peak_stats reads 4:2:0 input only (h2s_set_input_subsampling is 4:2:2 / 4:4:4)");
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   if (in->location != H2S_LOC_DEVICE) return fail(c, H2S_E_INVALID_ARG, "h2s_peak_stats takes device frames");
   if (nframes == 0) return 0;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   h2s_frames out = *in;                       // geometry only: the statistics read the input planes
-  fill_geometry(&k, in, &out, nframes, c->in_layout, H2S_LAYOUT_PLANAR);
+  fill_geometry(&k, in, &out, nframes, c->in_fmt, PLANAR_420);
   if ((rc = peak_order(c, s)) || (rc = frame_stats(c, k, s, nullptr, nullptr))) return rc;
   std::vector<double2> st(nframes);
   hipError_t e = hipMemcpyAsync(st.data(), c->d_fstat, nframes * sizeof(double2), hipMemcpyDeviceToHost, s);
@@ -1648,13 +1647,13 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     const h2s_frames ci = frames_at(&din, f0), co = frames_at(&dout, f0);
     if (host_in) {
       const h2s_frames hi = frames_at(in, f0);
-      if ((e = copy_frames(&ci, &hi, nf, s_in, r.in_layout, r.in_sub)) != hipSuccess) what = "host->device copy";
+      if ((e = copy_frames(&ci, &hi, nf, s_in, r.in_fmt)) != hipSuccess) what = "host->device copy";
       else if ((e = hipEventRecord(c->pev[i].ev, s_in)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_cmp, c->pev[i].ev, 0)) != hipSuccess) what = "pipeline ordering";
       if (what) break;
     }
     if (i == 0) timing_begin(c, s_cmp);
-    fill_geometry(&k, &ci, &co, nf, r.in_layout, r.out_layout, r.in_sub);
+    fill_geometry(&k, &ci, &co, nf, r.in_fmt, r.out_fmt);
     if (dyn_peak) {
       if (int rc = run_dynamic_peak(c, k, r.on(s_cmp))) {
         sync_all();
@@ -1667,7 +1666,7 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
       const h2s_frames ho = frames_at(out, f0);
       if ((e = hipEventRecord(c->pev[kMaxChunks + i].ev, s_cmp)) != hipSuccess) what = "pipeline event";
       else if ((e = hipStreamWaitEvent(s_out, c->pev[kMaxChunks + i].ev, 0)) != hipSuccess) what = "pipeline ordering";
-      else if ((e = copy_frames(&ho, &co, nf, s_out, r.out_layout)) != hipSuccess) what = "device->host copy";
+      else if ((e = copy_frames(&ho, &co, nf, s_out, r.out_fmt)) != hipSuccess) what = "device->host copy";
     }
   }
   if (what) {  // drain whatever was queued before returning the caller's buffers
@@ -1687,17 +1686,16 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
 
 // h2s_process for the two layouts given (the context's own for its callers'
 // sets; a preview's chain output is planar whatever the context's is).
-// Nothing it calls reads c->in_layout / c->out_layout / c->in_sub
-// (in_sub: the input's chroma subsampling, the context's for every caller)
+// Nothing it calls reads c->in_fmt / c->out_fmt
 static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
-                          int in_layout, int out_layout, int in_sub) {
+                          Format in_fmt, Format out_fmt) {
   if (nframes < 0) return fail(c, H2S_E_INVALID_ARG, "nframes < 0");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_subsampling(c, k, in_layout, in_sub))) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_layout, in_sub))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output", out_layout))) return rc;
+  if ((rc = check_subsampling(c, k, in_fmt))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_fmt))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", out_fmt))) return rc;
   if (in->width != out->width || in->height != out->height)
     return fail(c, H2S_E_INVALID_ARG, "input and output frame sizes differ");
   if (nframes == 0) return 0;
@@ -1706,16 +1704,15 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
 
   // host sets are staged: input, then (256-byte aligned) output
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
-  const size_t ib = host_in ? (frame_bytes(in, in_sub) * nframes + 255) / 256 * 256 : 0;
-  const size_t ob = host_out ? frame_bytes(out) * nframes : 0;
+  const size_t ib = host_in ? (frame_bytes(in, in_fmt) * nframes + 255) / 256 * 256 : 0;
+  const size_t ob = host_out ? frame_bytes(out, out_fmt) * nframes : 0;
   if ((host_in || host_out) && (rc = c->d_stage.reserve(c, ib + ob, "staging"))) return rc;
-  const h2s_frames din = device_view(in, c->d_stage, in_layout, in_sub), dout = device_view(out, c->d_stage + ib, out_layout);
-  fill_geometry(&k, &din, &dout, nframes, in_layout, out_layout, in_sub);
+  const h2s_frames din = device_view(in, c->d_stage, in_fmt), dout = device_view(out, c->d_stage + ib, out_fmt);
+  fill_geometry(&k, &din, &dout, nframes, in_fmt, out_fmt);
   // fast path: the tile kernel over whole 64 x 32 tiles; the generic kernel
   // covers the rest (choose_path / fast_params_ok) and the ragged columns
-  const Route r{choose_path(c, k, &din, &dout, out8),
-                vec_ok(&din, false, in_layout, in_sub) && vec_ok(&dout, out8, out_layout),
-                out8, in_layout, out_layout, s, in_sub};
+  const Route r{choose_path(c, k, &din, &dout, out8, in_fmt, out_fmt),
+                vec_ok(&din, false, in_fmt) && vec_ok(&dout, out8, out_fmt), out8, in_fmt, out_fmt, s};
   if (r.tile() && k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) return rc;
   // BICUBIC chroma (generic two-pass, or k_tile pass 1) uses the context scratch
   const bool two_pass = c->params.chroma_filter == H2S_CHROMA_BICUBIC;
@@ -1733,7 +1730,7 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
   if ((host_in || host_out) && nframes > 1 && !c->serial_host)
     return process_pipelined(c, k, in, out, din, dout, r, dyn_peak);
   if (host_in) {
-    hipError_t e = copy_frames(&din, in, nframes, s, in_layout, in_sub);
+    hipError_t e = copy_frames(&din, in, nframes, s, in_fmt);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "host->device copy"));
   }
   timing_begin(c, s);
@@ -1751,7 +1748,7 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
   if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "kernel launch"));
   timing_end(c, s);
   if (host_out) {
-    e = copy_frames(out, &dout, nframes, s, out_layout);
+    e = copy_frames(out, &dout, nframes, s, out_fmt);
     if (e != hipSuccess) return queued_exit(c, s, hip_fail(c, e, "device->host copy"));
   }
   if (two_pass && (rc = c->chr_use.mark(c, s, "two-pass event"))) return queued_exit(c, s, rc);
@@ -1765,7 +1762,7 @@ static int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* ou
 
 int h2s_process(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, void* hip_stream) {
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
-  return process_frames(c, in, out, nframes, (hipStream_t)hip_stream, c->in_layout, c->out_layout, c->in_sub);
+  return process_frames(c, in, out, nframes, (hipStream_t)hip_stream, c->in_fmt, c->out_fmt);
 }
 
 int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb, int out_location,
@@ -1776,8 +1773,8 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_subsampling(c, k, c->in_layout, c->in_sub))) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub))) return rc;
+  if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t npx = (size_t)in->width * in->height, ob = npx * 3 * sizeof(float);
@@ -1785,26 +1782,26 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   // (host output) and one output frame for the tile kernel's own stores
   h2s_frames fo{};
   fo.width = in->width, fo.height = in->height, fo.bits = c->params.bits_out, fo.location = H2S_LOC_DEVICE;
-  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in, c->in_sub) + 255) / 256 * 256 : 0;
-  const size_t fb = (frame_bytes(&fo) + 255) / 256 * 256, pb = out_location == H2S_LOC_HOST ? ob : 0;
+  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in, c->in_fmt) + 255) / 256 * 256 : 0;
+  const size_t fb = (frame_bytes(&fo, PLANAR_420) + 255) / 256 * 256, pb = out_location == H2S_LOC_HOST ? ob : 0;
   Dev<uint8_t> scratch;  // freed on every exit, after s has been waited for
   if ((rc = scratch.reserve(c, ib + fb + pb + 256, "debug"))) return rc;
   uint8_t* base = scratch;
-  const h2s_frames din = device_view(in, base, c->in_layout, c->in_sub);
+  const h2s_frames din = device_view(in, base, c->in_fmt);
   hipError_t e;
-  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_layout, c->in_sub)) != hipSuccess)
+  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_fmt)) != hipSuccess)
     return hip_fail(c, e, "debug copy");
-  fo = tight(&fo, base + ib, H2S_LAYOUT_PLANAR);   // (the call's own planar scratch frame)
+  fo = tight(&fo, base + ib, PLANAR_420);   // (the call's own planar scratch frame)
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
-  fill_geometry(&k, &din, &fo, 1, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub);
+  fill_geometry(&k, &din, &fo, 1, c->in_fmt, PLANAR_420);
   const bool out8 = c->params.bits_out == 8;
-  const Route r{choose_path(c, k, &din, &fo, out8), false, out8, c->in_layout, H2S_LAYOUT_PLANAR, s, c->in_sub};
+  const Route r{choose_path(c, k, &din, &fo, out8, c->in_fmt, PLANAR_420), false, out8, c->in_fmt, PLANAR_420, s};
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
   // (4:2:0 input: there are no debug instances of the tile kernel for 4:2:2 /
   // 4:4:4 input, whose planes are the generic kernel's whatever the path)
   e = h2s::launch_debug(k, stage, dout, s);
-  if (e == hipSuccess && r.tile() && c->in_sub == H2S_SUB_420) {
+  if (e == hipSuccess && r.tile() && c->in_fmt.sub == H2S_SUB_420) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
       return rc;
@@ -1862,7 +1859,7 @@ int h2s_set_frame_layout(h2s_ctx* c, int in_layout, int out_layout) {
   auto known = [](int l) { return l == H2S_LAYOUT_PLANAR || l == H2S_LAYOUT_SEMI; };
   if (!known(in_layout) || !known(out_layout)) return fail(c, H2S_E_INVALID_ARG, "unknown frame layout");
   // (only the arguments of later launches change: nothing queued reads these)
-  c->in_layout = in_layout, c->out_layout = out_layout;
+  c->in_fmt.layout = in_layout, c->out_fmt.layout = out_layout;
   return 0;
 }
 
@@ -1871,7 +1868,7 @@ int h2s_set_input_subsampling(h2s_ctx* c, int subsampling) {
   if (subsampling != H2S_SUB_420 && subsampling != H2S_SUB_422 && subsampling != H2S_SUB_444)
     return fail(c, H2S_E_INVALID_ARG, "unknown chroma subsampling");
   // (only the arguments of later launches change: nothing queued reads this)
-  c->in_sub = subsampling;
+  c->in_fmt.sub = subsampling;
   return 0;
 }
 
@@ -1880,14 +1877,14 @@ int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_subsampling(c, k, c->in_layout, c->in_sub))) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_layout))) return rc;
+  if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_fmt))) return rc;
   // host sets are staged into tight device copies, whose alignment decides
   uint8_t* fake = (uint8_t*)(uintptr_t)4096;
-  const h2s_frames din = device_view(in, fake, c->in_layout, c->in_sub), dout = device_view(out, fake, c->out_layout);
-  fill_geometry(&k, &din, &dout, 1, c->in_layout, c->out_layout, c->in_sub);
-  return choose_path(c, k, &din, &dout, c->params.bits_out == 8);
+  const h2s_frames din = device_view(in, fake, c->in_fmt), dout = device_view(out, fake, c->out_fmt);
+  fill_geometry(&k, &din, &dout, 1, c->in_fmt, c->out_fmt);
+  return choose_path(c, k, &din, &dout, c->params.bits_out == 8, c->in_fmt, c->out_fmt);
 }
 
 // ---- preview ---------------------------------------------------------------
@@ -1947,7 +1944,7 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
   if (!c->params_set) return fail(c, H2S_E_INVALID_ARG, "h2s_set_params was not called");
   if (c->params.bits_out != 8)
     return fail(c, H2S_E_INVALID_ARG, "preview needs params.bits_out == 8 (the chain's yuv420p)");
-  int rc = check_frames(c, in, c->params.bits_in, "input", c->in_layout, c->in_sub);
+  int rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt);
   if (rc) return rc;
   const int W = in->width, H = in->height;
   const bool scale = out_w != W || out_h != H;
@@ -2008,7 +2005,7 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
   // layout the context writes its callers' frames in
   h2s_frames y8{};
   y8.width = W, y8.height = H, y8.bits = 8, y8.location = H2S_LOC_DEVICE;
-  y8 = tight(&y8, base, H2S_LAYOUT_PLANAR);
+  y8 = tight(&y8, base, PLANAR_420);
   if (c->params.peak_detect) {
     // libplacebo branch: the reference converts each preview frame in its own
     // ffmpeg run (extract_frames_with_gpu_conversion_batch loops
@@ -2035,12 +2032,12 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
       }
       if ((e = hipMemsetAsync(c->d_pk, 0, pb, s)) != hipSuccess)
         return restored(queued_exit(c, s, hip_fail(c, e, "peak state reset")));
-      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub))) return restored(rc);
+      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_fmt, PLANAR_420))) return restored(rc);
     }
     if ((e = hipMemcpyAsync(c->d_pk, c->d_pk + 1, pb, hipMemcpyDeviceToDevice, s)) != hipSuccess)
       return queued_exit(c, s, hip_fail(c, e, "peak state restore"));
     if ((rc = peak_done(c, s))) return queued_exit(c, s, rc);
-  } else if ((rc = process_frames(c, in, &y8, nframes, s, c->in_layout, H2S_LAYOUT_PLANAR, c->in_sub))) {  // one launch for the batch
+  } else if ((rc = process_frames(c, in, &y8, nframes, s, c->in_fmt, PLANAR_420))) {  // one launch for the batch
     return rc;
   }
   hipError_t e = hipSuccess;

@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""SHA-256 of the output bytes of every frame form the kernels read or write,
+for the library H2S_LIB names (default: the tree's): two builds whose lines
+are equal convert every form identically.  The suite holds 4:2:2 / 4:4:4 input
+to the oracle within a tolerance only, so a change that must not alter a
+single output code is held to this instead.  GPU box.
+
+Every case: 3 frames, seed 11, a 17^3 LUT, device sets.  4:2:0 input in all
+four layout combinations, 4:2:2 / 4:4:4 input (the exact upsamples of the
+4:2:0 source, tests/subsampling_ref.py) into both output layouts.  Sizes: one
+tile, 3 x 3 tiles, a bottom tile with 6 live rows, tile + k_process columns,
+the generic kernel, and 130x98 / 194x66 with rows padded to 16 bytes (the tile
+kernel's interior / border equalities; the hash covers the padding too).
+One JSON line: {"chain/kind/WxH/sub/in->out": sha256, ...}, keys sorted.
+
+  [H2S_LIB=/path/to/libh2s.so] python scripts/format_checksums.py [OUT.json]
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, 'hdr-to-sdr_amd'), REPO, os.path.join(REPO, 'tests')]
+
+NF, SEED, LUT_N = 3, 11, 17
+TIGHT = [(64, 32), (192, 96), (192, 70), (208, 64), (70, 34)]
+PADDED = [(130, 98), (194, 66)]
+# name -> (parameters, content kinds, 4:2:2 / 4:4:4 input too)
+CHAINS = {
+    'hable_lut_g22': (dict(tonemapper='hable', gamma=2.2, bits_in=10, bits_out=10), ('edges', 'smooth'), True),
+    'reinhard_8_dither': (dict(tonemapper='reinhard', bits_out=8, dither='ordered'), ('smooth',), True),
+    'mobius_hlg12': (dict(tonemapper='mobius', transfer='arib-std-b67', bits_in=12, bits_out=12), ('smooth',), True),
+    'lp_bt2390_peak_detect': (dict(tonemapper='bt.2390', peak_detect=True, maxcll=4000.0), ('smooth',), False),
+    'hable_bicubic': (dict(tonemapper='hable', gamma=2.2, chroma_filter='bicubic'), ('smooth',), True),
+}
+FORMS = [('420', il, ol) for il in ('planar', 'semi') for ol in ('planar', 'semi')] + \
+        [(sub, 'planar', ol) for sub in ('422', '444') for ol in ('planar', 'semi')]
+
+
+def main():
+    import torch
+
+    import hdr2sdr
+    import subsampling_ref as SR
+    from hdr2sdr.frames import FrameBatch
+    from hdr2sdr.synth import synth_frames
+    from padded_frames import RowPadded
+
+    lattice = hdr2sdr.generate_lattice(LUT_N)
+    res = {}
+    tm = hdr2sdr.Tonemapper(0)
+    for name, (kw, kinds, subs) in CHAINS.items():
+        params = hdr2sdr.TonemapParams(**kw)
+        tm.set_params(params)
+        tm.set_lut(lattice)
+        for kind in kinds:
+            for W, H in TIGHT + PADDED:
+                pad = (W, H) in PADDED
+                fb = SR.round8(synth_frames(kind, NF, W, H, params.bits_in, device='cpu', seed=SEED).to_numpy())
+                host = {('420', 'planar'): fb, ('420', 'semi'): fb.to_layout('semi')}
+                if subs:
+                    host.update({(s, 'planar'): b for s, b in SR.exact_inputs(fb).items()})
+                for sub, il, ol in FORMS:
+                    if (sub, il) not in host:
+                        continue
+                    h = host[(sub, il)]
+                    if pad:
+                        src = RowPadded(NF, W, H, params.bits_in, il, sub).load(h)
+                        dst = RowPadded(NF, W, H, params.bits_out, ol)
+                    else:
+                        src = h.to_torch('cuda')
+                        dst = FrameBatch.empty_torch(NF, W, H, params.bits_out, 'cuda', ol)
+                        dst.buf.fill_(0x55 if params.bits_out == 8 else 0x5555)
+                    if params.peak_detect:
+                        tm.reset_peak()
+                    tm.process(src, dst)
+                    torch.cuda.synchronize()
+                    out = dst.raw() if pad else dst.to_numpy().buf
+                    res[f'{name}/{kind}/{W}x{H}/{sub}/{il}->{ol}'] = \
+                        hashlib.sha256(np.ascontiguousarray(out).tobytes()).hexdigest()
+    tm.close()
+    line = json.dumps(res, sort_keys=True)
+    print(line)
+    if len(sys.argv) > 1:
+        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
+        with open(sys.argv[1], 'w') as fh:
+            fh.write(line + '\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
