@@ -22,8 +22,7 @@ enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2
 hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s);
 hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s);
 bool fast_supported(int tonemap);
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg = 0,
-                       int sub = 0);
+hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub = 0);
 hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float* wy8, bool out8, hipStream_t s);
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st);
 hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
@@ -1212,8 +1211,8 @@ static int tiled_width(const KParams& k) { return k.W & ~(h2s::TBW - 1); }
 // what a tile launch does beside the plain conversion
 struct TileOpts {
   const h2s::CurveConsts* cv_frames = nullptr;   // dynamic peak: one curve record per frame of the launch
-  int dbg = 0;                 // > 0: the debug instance for that stage, which writes
-  float* dbg_out = nullptr;    //      frame 0's float planes here
+  int dbg = 0;                 // > 0: the debug instance, which writes that stage's
+  float* dbg_out = nullptr;    //      float planes of frame 0 here
   float2* chr444 = nullptr;    // BICUBIC pass 1: every pixel's (Cb, Cr) here, no chroma planes
 };
 
@@ -1242,6 +1241,7 @@ static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& 
   F.tpb = c->tiles_per_block;
   F.cv_frames = o.cv_frames;
   F.dbg = o.dbg_out;
+  F.dbg_stage = o.dbg;
   F.dbg_w = k.W;
   F.dbg_lut = c->d_lut;
   F.inv_nm1 = 1.0f / (float)(c->lut_n - 1);
@@ -1249,7 +1249,7 @@ static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& 
   F.chr_w = k.W;
   F.inv_c56 = 1.0f / F.c56;
   const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
-  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, o.dbg, k.sub);
+  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, k.sub);
 }
 
 // the generic kernel over a column range of k's frames: every column, or the

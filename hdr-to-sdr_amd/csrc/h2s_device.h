@@ -236,8 +236,9 @@ struct FastParams : CurveConsts {
   // S1 PQ EOTF (x 10000/npl) as a piecewise cubic: segment i covers
   // E in [i, i+1)/PQ_SEG, coefficients (c3, c2, c1, c0) of t = E*PQ_SEG - i
   const float4* pq_tab;
-  // debug instances (k_tile<..., DBG>): stage planes of frame 0, row pitch
-  // dbg_w floats; the float4 RGB lattice for stage 4; 1 / (N-1)
+  // debug instances (k_tile<..., DBG = 1>): stage planes of frame 0, row pitch
+  // dbg_w floats; the float4 RGB lattice for stage 4; 1 / (N-1); the stage
+  // whose planes are written is dbg_stage (the struct's last member)
   float* dbg;
   int dbg_w;
   const float4* dbg_lut;
@@ -255,6 +256,10 @@ struct FastParams : CurveConsts {
   // input's chroma plane is icw x ich samples (W/2 x H, or W x H); cw and ch
   // above stay the output's W/2 x H/2
   int icw, ich;
+  // the h2s_stage (1..5) whose planes a debug instance writes to dbg, read by
+  // the k_tile<..., DBG = 1> instances only (launch-uniform branches there;
+  // last again, so that no other field moves)
+  int dbg_stage;
 };
 
 constexpr int TBW = 64, TBH = 32;   // k_tile: luma tile of one block

@@ -7,33 +7,15 @@
 namespace h2s {
 
 H2S_TILE_INSTANCE(0, 0, false)
-H2S_TILE_EXTERN(0, 1, false)   // h2s_fast_lp.hip
-H2S_TILE_EXTERN(1, 0, false)
-H2S_TILE_EXTERN(1, 1, false)
-H2S_TILE_EXTERN(2, 0, false)
-H2S_TILE_EXTERN(2, 1, false)
-H2S_TILE_EXTERN(3, 0, false)
-H2S_TILE_EXTERN(3, 1, false)
-H2S_TILE_EXTERN(4, 0, false)
-H2S_TILE_EXTERN(4, 1, false)
-H2S_TILE_EXTERN(5, 0, false)
-H2S_TILE_EXTERN(5, 1, false)
-// the instances for semi-planar frame sets (h2s_fast_semi*.hip)
-H2S_TILE_EXTERN(0, 0, true)
-H2S_TILE_EXTERN(0, 1, true)
-H2S_TILE_EXTERN(1, 0, true)
-H2S_TILE_EXTERN(1, 1, true)
-H2S_TILE_EXTERN(2, 0, true)
-H2S_TILE_EXTERN(2, 1, true)
-H2S_TILE_EXTERN(3, 0, true)
-H2S_TILE_EXTERN(3, 1, true)
-H2S_TILE_EXTERN(4, 0, true)
-H2S_TILE_EXTERN(4, 1, true)
-H2S_TILE_EXTERN(5, 0, true)
-H2S_TILE_EXTERN(5, 1, true)
-// the instances for 4:2:2 / 4:4:4 input (h2s_fast_sub422.hip, h2s_fast_sub444.hip)
-H2S_TILE_SUB_EXTERN(1)
-H2S_TILE_SUB_EXTERN(2)
+H2S_TILE_EXTERN(0, 1, false)     // h2s_fast_lp.hip
+H2S_TILE_EXTERN(0, 0, true)      // h2s_fast_semi.hip: the instances for semi-planar frame sets
+H2S_TILE_EXTERN(0, 1, true)      // h2s_fast_lp_semi.hip
+H2S_TILE_EXTERN(0, 0, true, 1)   // h2s_fast_sub422.hip: 4:2:2 input
+H2S_TILE_EXTERN(0, 0, true, 2)   // h2s_fast_sub444.hip: 4:4:4 input
+H2S_TILE_EXTERN(1, 0, false)     // h2s_debug.hip: the debug instances
+H2S_TILE_EXTERN(1, 1, false)     // h2s_debug_lp.hip
+H2S_TILE_EXTERN(1, 0, true)      // h2s_debug_semi.hip
+H2S_TILE_EXTERN(1, 1, true)      // h2s_debug_lp_semi.hip
 
 // YUV-premultiplied lattice (12-byte records, .cube order):
 // ((16 + 219*Y)*s + 0.5, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
@@ -61,11 +43,11 @@ bool fast_supported(int tonemap) { return tonemap >= 4 && tonemap <= 8; }
 
 // desat: 0 off, 1 weighted luma, 2 RGB-coefficient luma (vf_tonemap's; the
 // libplacebo curves have none).  lp: the libplacebo branch (every operator).
-// dbg: 0 = the
-// product kernel; 1..5 = its debug instance for that h2s_stage (F.dbg set)
+// F.dbg_stage: 0 = the product kernel; 1..5 = the chain's debug instance, which
+// also writes that h2s_stage's planes (F.dbg set)
 // sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4: CPU chain product
 // instances only; anything else there is an error, never another kernel)
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int dbg, int sub) {
+hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub) {
   const long long nt = (long long)F.nbx * F.nby * F.nframes;
   if (nt == 0) return hipSuccess;
   const long long nb = (nt + F.tpb - 1) / F.tpb;
@@ -75,28 +57,19 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   // profiles/r03/ablations/blocks_per_cu.log)
   const size_t lds = ((size_t)F.eq_n * sizeof(uint16_t) + 15) & ~(size_t)15;
   if (tm == 7 || tm == 8 || lp) desat = 0;
-  // planar sets on both sides: the instances without the layout branches
-  const bool semi = F.in_semi || F.out_semi;
+  const bool dbg = F.dbg_stage != 0;
   if (sub) {
     if (lp || dbg || F.in_semi || sub > 2) return hipErrorInvalidValue;
     return sub == 1 ? launch_tile<0, 0, true, 1>(F, trc, tm, desat, grid, lds, s)
                     : launch_tile<0, 0, true, 2>(F, trc, tm, desat, grid, lds, s);
   }
-#define H2S_DISPATCH(D)                                                                                  \
-  if (semi)                                                                                              \
-    return lp ? launch_tile<D, 1, true>(F, trc, tm, desat, grid, lds, s)                                 \
-              : launch_tile<D, 0, true>(F, trc, tm, desat, grid, lds, s);                                \
-  return lp ? launch_tile<D, 1, false>(F, trc, tm, desat, grid, lds, s)                                  \
-            : launch_tile<D, 0, false>(F, trc, tm, desat, grid, lds, s)
-  switch (dbg) {
-    case 0: H2S_DISPATCH(0);
-    case 1: H2S_DISPATCH(1);
-    case 2: H2S_DISPATCH(2);
-    case 3: H2S_DISPATCH(3);
-    case 4: H2S_DISPATCH(4);
-    default: H2S_DISPATCH(5);
-  }
-#undef H2S_DISPATCH
+  // planar sets on both sides: the instances without the layout branches
+  const bool semi = F.in_semi || F.out_semi;
+  auto* launch = dbg ? (lp ? (semi ? launch_tile<1, 1, true> : launch_tile<1, 1, false>)
+                           : (semi ? launch_tile<1, 0, true> : launch_tile<1, 0, false>))
+                     : (lp ? (semi ? launch_tile<0, 1, true> : launch_tile<0, 1, false>)
+                           : (semi ? launch_tile<0, 0, true> : launch_tile<0, 0, false>));
+  return launch(F, trc, tm, desat, grid, lds, s);
 }
 
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st) {

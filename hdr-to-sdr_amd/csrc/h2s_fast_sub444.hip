@@ -8,6 +8,6 @@
 
 namespace h2s {
 
-H2S_TILE_SUB_INSTANCE(2)
+H2S_TILE_INSTANCE(0, 0, true, 2)
 
 }  // namespace h2s

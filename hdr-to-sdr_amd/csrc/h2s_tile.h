@@ -1,6 +1,6 @@
 // h2s_tile.h — the tile kernel k_tile (the specialised fast path of the fused
-// tone-map kernel), its instance table and a per-DBG dispatcher.  Included by
-// h2s_fast.hip (product instances) and h2s_fast_dbg*.hip (debug instances),
+// tone-map kernel), its instance table and a per-chain dispatcher.  Included
+// by h2s_fast*.hip (product instances) and h2s_debug*.hip (debug instances),
 // so the instances compile as separate translation units.
 //
 // Same chain as k_generic (h2s_kernels.hip) and oracle/h2s_oracle.c, restated
@@ -471,7 +471,9 @@ struct StepK {
 
 // S1 + S2 of one pixel (px_chain, lp_front): staged luma ybs (Y*ys + y_off,
 // +1 on PQ), x8-upsampled centred chroma U, V -> the tone-mapped linear
-// R, G, B, with the dark re-run below.  dput: the debug planes' writer (DBG)
+// R, G, B, with the dark re-run below.  dput: the debug planes' writer (DBG
+// = 1: the planes of F.dbg_stage, a launch-uniform test at each site; DBG = 0
+// compiles every site away)
 template <int TRC, int TM, int DESAT, int LP, int DBG, bool NOEX, class DPut>
 __device__ __forceinline__ void lin_tone(const FastParams& F, const CurveConsts& cv, const float4* pq_lds,
                                          const float4* pqi_lds, const StepK& K, float ybs, float U, float V,
@@ -486,7 +488,7 @@ __device__ __forceinline__ void lin_tone(const FastParams& F, const CurveConsts&
   H2S_MARK("S1b EOTF");
   const bool safe = to_linear<TRC, ESC, NOEX>(F, pq_lds, er, eg, eb, r, gg, bl);
   H2S_MARKV("S2 tone", r, gg, bl);
-  if (DBG == 1) {   // the stage-1 planes with the first segment exact, as the dark re-run below gives them
+  if (DBG && F.dbg_stage == 1) {   // the stage-1 planes with the first segment exact, as the dark re-run below gives them
     float r1, g1, b1;
     to_linear<TRC, ESC, NOEX, true>(F, pq_lds, er, eg, eb, r1, g1, b1);
     dput(r1, g1, b1);
@@ -589,7 +591,7 @@ __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveCon
   float r, gg, bl;
   lin_tone<TRC, TM, DESAT, LP, DBG, NOEX>(F, cv, pq_lds, pqi_lds, K, ybs, U, V, dput, r, gg, bl);
   H2S_MARKV("S3 encode", r, gg, bl);
-  if (DBG == 2) dput(r, gg, bl);
+  if (DBG && F.dbg_stage == 2) dput(r, gg, bl);
   f3 o;
   if (LP && F.lut_off) {
     // LUT off: libplacebo's BT.2020 -> BT.709 matrix on the linear
@@ -603,12 +605,12 @@ __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveCon
     const float R = enc(F.m709[0] * r + F.m709[1] * gg + F.m709[2] * bl);
     const float G = enc(F.m709[3] * r + F.m709[4] * gg + F.m709[5] * bl);
     const float B = enc(F.m709[6] * r + F.m709[7] * gg + F.m709[8] * bl);
-    if (DBG == 3 || DBG == 4) dput(R * F.inv255, G * F.inv255, B * F.inv255);
+    if (DBG && (F.dbg_stage == 3 || F.dbg_stage == 4)) dput(R * F.inv255, G * F.inv255, B * F.inv255);
     o.x = fmaf(F.lp_ky[0], R, fmaf(F.lp_ky[1], G, fmaf(F.lp_ky[2], B, K.lp_cy)));
     o.y = fmaf(F.lp_kcb[0], R, fmaf(F.lp_kcb[1], G, F.lp_kcb[2] * B));
     o.z = fmaf(F.lp_kcr[0], R, fmaf(F.lp_kcr[1], G, F.lp_kcr[2] * B));
   } else if constexpr (LP) {
-    if (DBG == 3) {
+    if (DBG && F.dbg_stage == 3) {
       auto ev = [&](float x) {
         const float e = fexp2(fmaf(flog2(__builtin_amdgcn_fmed3f(x, 0.0f, F.lp_xmax)), 1.0f / 2.4f, F.lp_k1)) - F.lp_k2;
         return __builtin_amdgcn_fmed3f(e, 0.0f, 255.0f) * F.inv255;
@@ -618,7 +620,7 @@ __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveCon
     const unsigned v = lp_table_read(F, K, lut8v, spread_lds, r, gg, bl, qoff);
     const float R8 = (float)(v & 255u), G8 = (float)((v >> 8) & 255u), B8 = (float)((v >> 16) & 255u);   // (v_cvt_f32_ubyte0..2)
     H2S_MARK("S5 Y'CbCr");
-    if (DBG == 4) dput(R8 * F.inv255, G8 * F.inv255, B8 * F.inv255);
+    if (DBG && F.dbg_stage == 4) dput(R8 * F.inv255, G8 * F.inv255, B8 * F.inv255);
     o = lp_ycbcr(F, K, R8, G8, B8);
   } else {
     // lattice cell origins (cr, cg, cb) and fractions (dr, dg, db) per channel
@@ -729,8 +731,8 @@ __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveCon
                 __builtin_amdgcn_raw_buffer_load_b96(lut, base + ocn, 0, 0),
                 __builtin_amdgcn_raw_buffer_load_b96(lut, base, F.c111, 0));
     }
-    if (DBG == 3) dput((cr + dr) * F.inv_nm1, (cg + dg) * F.inv_nm1, (cb + db) * F.inv_nm1);   // = s exactly
-    if (DBG == 4) {  // same cell / corners / weights on the RGB lattice (12-byte record -> float4 index)
+    if (DBG && F.dbg_stage == 3) dput((cr + dr) * F.inv_nm1, (cg + dg) * F.inv_nm1, (cb + db) * F.inv_nm1);   // = s exactly
+    if (DBG && F.dbg_stage == 4) {  // same cell / corners / weights on the RGB lattice (12-byte record -> float4 index)
       const float4 q0 = F.dbg_lut[base / 12], q1 = F.dbg_lut[(base + om) / 12], q2 = F.dbg_lut[(base + ocn) / 12],
                    q3 = F.dbg_lut[(base + F.c111) / 12];
       dput(w0 * q0.x + w1 * q1.x + w2 * q2.x + w3 * q3.x, w0 * q0.y + w1 * q1.y + w2 * q2.y + w3 * q3.y,
@@ -738,7 +740,7 @@ __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveCon
     }
   }
   H2S_MARKV("S7 eq", o.x, o.y, o.z);
-  if (DBG == 5) dput(o.x - (EQM ? 0.0f : 0.5f) - ydq, 4.0f * o.y, 4.0f * o.z);
+  if (DBG && F.dbg_stage == 5) dput(o.x - (EQM ? 0.0f : 0.5f) - ydq, 4.0f * o.y, 4.0f * o.z);
   oyv = o.y, ozv = o.z;
   if constexpr (EQM) {
     // o.x = the luma quantiser input less 0.5 (the lattice records carry no
@@ -1210,10 +1212,12 @@ __device__ __forceinline__ void put_chroma_semi(const FastParams& F, const TileG
 // profiles/r03/ablations/io_wave*.  Issuing the stores of tile i-1 and the
 // loads of tile i+1 inside step 7, behind its gathers, measured 3-5 % slower:
 // profiles/r03/ablations/late_io*.)
-// DBG (debug instances only, never launched by h2s_process): 1..5 = also
-// write that h2s_stage's three float planes for frame 0 to F.dbg (W x H each)
-// from this kernel's own arithmetic — stage 4 blends the float4 RGB lattice
-// F.dbg_lut with the same cell, corners and weights as the Y'CbCr lattice.
+// DBG (0 or 1; 1 = the debug instances, never launched by h2s_process): run
+// the whole chain and also write the three float planes of h2s_stage
+// F.dbg_stage (1..5, a run-time field: one debug instance per chain serves
+// every stage) for frame 0 to F.dbg (W x H each) from this kernel's own
+// arithmetic — stage 4 blends the float4 RGB lattice F.dbg_lut with the same
+// cell, corners and weights as the Y'CbCr lattice.
 // LP = 1: the libplacebo branch (src/utils.py:444-460, BT.2390 / spline):
 // BT.1886 encode against the target black, 8-bit rgba download, lut3d's 8-bit
 // path on plain R'G'B' records (truncating output), BT.709 Y'CbCr at depth q
@@ -1248,6 +1252,7 @@ template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false, in
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TILE_WPE_LP : H2S_TILE_WPE))) void k_tile(
     const FastParams F) {
+  static_assert(DBG == 0 || DBG == 1, "the stage is F.dbg_stage, not a template value");
   static_assert(SUB == 0 || (LP == 0 && DBG == 0), "4:2:2 / 4:4:4 input: CPU chain product instances only");
   constexpr int YST = row_stride<LP>(), HST = YST;
   static_assert(TBH * C422_ST <= (CBH + 2) * HST && TBH * C444_ST <= 2 * (CBH + 2) * HST, "hrow holds the SUB windows");
@@ -1573,10 +1578,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   X(1, 5, 0, 1)       \
   X(1, 6, 0, 1)
 
-// one DBG value's instances (0 = product kernels; 1..5 = the debug instance
-// for that h2s_stage) of one chain (LPI 0: the CPU chain, 1: the libplacebo
-// branch), explicitly instantiated in exactly one .hip each: the two chains'
-// product instances compile in their own translation units, so each gets the
+// the product (DBG 0) or the debug (DBG 1: every h2s_stage, F.dbg_stage)
+// instances of one chain (LPI 0: the CPU chain, 1: the libplacebo branch),
+// explicitly instantiated in exactly one .hip each: the two chains' product
+// instances compile in their own translation units, so each gets the
 // scheduler that measured fastest for it (_build.py SOURCE_FLAGS)
 template <int DBG, int LPI, bool SEMI = false, int SUB = 0>
 hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 grid, size_t lds, hipStream_t s) {
@@ -1591,17 +1596,13 @@ hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 gri
 #undef X
   return hipErrorInvalidValue;
 }
-// (S: the SEMI instances, each chain's and stage's in a translation unit of their own)
-#define H2S_TILE_EXTERN(D, L, S) \
-  extern template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
-#define H2S_TILE_INSTANCE(D, L, S) \
-  template hipError_t launch_tile<D, L, S>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
-
-// the 4:2:2 / 4:4:4 input instances (SUB 1 / 2): the CPU chain's product
-// kernels with the output side's layout branches, one translation unit per SUB
-#define H2S_TILE_SUB_EXTERN(SUB) \
-  extern template hipError_t launch_tile<0, 0, true, SUB>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
-#define H2S_TILE_SUB_INSTANCE(SUB) \
-  template hipError_t launch_tile<0, 0, true, SUB>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+// launch_tile's arguments <DBG, LPI, SEMI[, SUB]>: each chain's planar and
+// SEMI instances in a translation unit of their own, and one per SUB for the
+// 4:2:2 / 4:4:4 input instances <0, 0, true, SUB> (the CPU chain's product
+// kernels with the output side's layout branches)
+#define H2S_TILE_EXTERN(...) \
+  extern template hipError_t launch_tile<__VA_ARGS__>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
+#define H2S_TILE_INSTANCE(...) \
+  template hipError_t launch_tile<__VA_ARGS__>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 
 }  // namespace h2s

@@ -27,7 +27,7 @@ HDR=0
 if grep -q '^+++ .*\.h[[:space:]]' "$PATCH"; then HDR=1; fi
 OBJS=()
 PIDS=()
-for s in h2s_fast_dbg345.hip h2s_fast_dbg12.hip h2s_fast_lp.hip h2s_fast.hip h2s_api.hip h2s_kernels.hip h2s_preview.hip h2s_cube.cpp; do
+for s in h2s_debug.hip h2s_debug_lp.hip h2s_fast_lp.hip h2s_fast.hip h2s_api.hip h2s_kernels.hip h2s_preview.hip h2s_cube.cpp; do
   if [ $s = h2s_fast.hip ] || [ $s = h2s_fast_lp.hip ] || [ $HDR = 1 ] || grep -q "^+++ .*/$s[[:space:]]" "$PATCH"; then
     extra=""
     if [ $s = h2s_kernels.hip ]; then extra="-ffp-contract=off"; fi

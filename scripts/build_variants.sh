@@ -20,11 +20,11 @@ for spec in "$@"; do
   [ "$flags" = "$spec" ] && flags=""
   (
     # DBG=1: the debug instances (h2s_debug_float) get the flags too
-    d12="$O/h2s_fast_dbg12.hip.o"; d345="$O/h2s_fast_dbg345.hip.o"
+    dcpu="$O/h2s_debug.hip.o"; dlp="$O/h2s_debug_lp.hip.o"
     if [ "${DBG:-0}" = 1 ]; then
-      d12="$V/dbg12_$name.o"; d345="$V/dbg345_$name.o"
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $flags -c -o "$d12" "$C/h2s_fast_dbg12.hip" &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $flags -c -o "$d345" "$C/h2s_fast_dbg345.hip" || exit 1
+      dcpu="$V/dbgcpu_$name.o"; dlp="$V/dbglp_$name.o"
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $flags -c -o "$dcpu" "$C/h2s_debug.hip" &&
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $flags -c -o "$dlp" "$C/h2s_debug_lp.hip" || exit 1
     fi
     # KERN=1: h2s_kernels.hip (generic kernel, peak statistics) gets the flags too
     kern="$O/h2s_kernels.hip.o"
@@ -35,8 +35,8 @@ for spec in "$@"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $MMC $flags -c -o "$V/fast_$name.o" "$C/h2s_fast.hip" &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $flags -c -o "$V/fastlp_$name.o" "$C/h2s_fast_lp.hip" &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$V/libh2s_$name.so" "$V/fast_$name.o" "$V/fastlp_$name.o" \
-      "$d345" "$d12" "$O/h2s_api.hip.o" "$kern" \
-      "$O/h2s_preview.hip.o" "$O/h2s_cube.cpp.o" && rm -f "$V/fast_$name.o" "$V/fastlp_$name.o" "$V/dbg12_$name.o" "$V/dbg345_$name.o" "$V/kern_$name.o"
+      "$dlp" "$dcpu" "$O/h2s_api.hip.o" "$kern" \
+      "$O/h2s_preview.hip.o" "$O/h2s_cube.cpp.o" && rm -f "$V/fast_$name.o" "$V/fastlp_$name.o" "$V/dbgcpu_$name.o" "$V/dbglp_$name.o" "$V/kern_$name.o"
   ) &
   pids+=($!)
 done

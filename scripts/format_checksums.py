@@ -14,6 +14,14 @@ kernel's interior / border equalities; the hash covers the padding too).
 One JSON line: {"chain/kind/WxH/sub/in->out": sha256, ...}, keys sorted.
 
   [H2S_LIB=/path/to/libh2s.so] python scripts/format_checksums.py [OUT.json]
+
+--debug-planes OUT.npz instead saves the h2s_debug_float planes of stages 1-5
+(the tile kernel's debug instances), so that two builds' planes can be compared
+value by value: every tests/float_gate.py FLOAT_CFGS entry x edges / smooth,
+one frame, planar and semi-planar input, at 64x32, 192x70 and 208x64; keys
+"cfg/kind/WxH/layout/stage".
+
+  [H2S_LIB=...] python scripts/format_checksums.py --debug-planes OUT.npz
 """
 import hashlib
 import json
@@ -40,7 +48,34 @@ FORMS = [('420', il, ol) for il in ('planar', 'semi') for ol in ('planar', 'semi
         [(sub, 'planar', ol) for sub in ('422', '444') for ol in ('planar', 'semi')]
 
 
+def debug_planes(path):
+    import hdr2sdr
+    from float_gate import FLOAT_CFGS
+    from hdr2sdr.synth import synth_frames
+
+    lattice = hdr2sdr.generate_lattice(LUT_N)
+    res = {}
+    tm = hdr2sdr.Tonemapper(0)
+    for name, kw in sorted(FLOAT_CFGS.items()):
+        params = hdr2sdr.TonemapParams(**kw)
+        tm.set_params(params)
+        tm.set_lut(lattice)
+        for kind in ('edges', 'smooth'):
+            for W, H in [(64, 32), (192, 70), (208, 64)]:
+                planar = synth_frames(kind, 1, W, H, params.bits_in, device='cpu', seed=SEED).to_torch('cuda')
+                for layout, src in (('planar', planar), ('semi', planar.to_layout('semi'))):
+                    for stage in (1, 2, 3, 4, 5):
+                        res[f'{name}/{kind}/{W}x{H}/{layout}/{stage}'] = tm.debug_float(src, stage)
+    tm.close()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez_compressed(path, **res)
+    print(f'{len(res)} plane sets -> {path}')
+    return 0
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == '--debug-planes':
+        return debug_planes(sys.argv[2])
     import torch
 
     import hdr2sdr
