@@ -55,9 +55,18 @@ int hip_fail(h2s_ctx* c, hipError_t e, const char* what);
 // unused) and its chroma subsampling (enum h2s_subsampling: chroma planes of
 // width >> cxs samples x height >> cys rows; a semi-planar set and every
 // output set is 4:2:0).  Whatever reads an h2s_frames takes its Format, never
-// defaulted; the planes' sizes are written here and nowhere else
+// defaulted; the planes' sizes are written here and nowhere else.  An input
+// set also carries its source tags (h2s_set_input_tags): the colour range of
+// its codes (enum h2s_range) and its 4:2:0 chroma location (enum
+// h2s_chroma_loc); the kernels' S1 constants and vertical taps follow from
+// them in fill_geometry.  An output set is always limited range
 struct Format {
   int layout, sub;
+  int range = H2S_RANGE_LIMITED, loc = H2S_CHROMA_LEFT;
+  bool full() const { return range == H2S_RANGE_FULL; }
+  // chroma rows co-sited with the even luma rows: 4:2:0 only (a 4:2:2 / 4:4:4
+  // set has no vertical pass, the tag has no effect there)
+  bool vco() const { return loc == H2S_CHROMA_TOPLEFT && sub == H2S_SUB_420; }
   bool semi() const { return layout == H2S_LAYOUT_SEMI; }
   int cxs() const { return sub == H2S_SUB_444 ? 0 : 1; }
   int cys() const { return sub == H2S_SUB_420 ? 1 : 0; }
@@ -205,7 +214,8 @@ struct __attribute__((visibility("hidden"))) h2s_ctx {
   bool fast_enabled = true;
   bool lp_exact = false;  // H2S_OPT_LP_EXACT
   // how later calls read `in` and write `out`: h2s_set_frame_layout sets both
-  // layouts, h2s_set_input_subsampling in_fmt.sub (the output is always 4:2:0)
+  // layouts, h2s_set_input_subsampling in_fmt.sub (the output is always 4:2:0),
+  // h2s_set_input_tags in_fmt.range and in_fmt.loc
   Format in_fmt = PLANAR_420, out_fmt = PLANAR_420;
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
@@ -736,6 +746,10 @@ hipError_t copy_frames(const h2s_frames* dst, const h2s_frames* src, int nframes
 // their high bits
 // The input's chroma plane (h2s_set_input_subsampling) is icw x ich; cw, ch,
 // ngx and total stay the output's
+// The input's tags (h2s_set_input_tags): a full-range set replaces the S1
+// depth-conversion constants resolve() wrote (zimg's full-range integer to
+// float conversion: Y' = code / (2^b - 1), Cb, Cr = (code - 2^(b-1)) /
+// (2^b - 1)); resolve_fast folds the same from k.full
 void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int nframes, Format in_fmt,
                    Format out_fmt) {
   k->W = in->width;
@@ -743,6 +757,12 @@ void fill_geometry(KParams* k, const h2s_frames* in, const h2s_frames* out, int 
   k->cw = in->width / 2;
   k->ch = in->height / 2;
   k->sub = in_fmt.sub, k->icw = in->width >> in_fmt.cxs(), k->ich = in->height >> in_fmt.cys();
+  k->full = in_fmt.full() ? 1 : 0, k->vco = in_fmt.vco() ? 1 : 0;
+  if (k->full) {
+    const double top = (double)((1 << in->bits) - 1);
+    k->y_scale = (float)(1.0 / top), k->y_off = 0.0f;
+    k->c_scale = (float)(1.0 / top), k->c_off = (float)(-(double)(1 << (in->bits - 1)) / top);
+  }
   k->ngx = (k->cw + 3) / 4;
   k->nframes = nframes;
   k->total = (long long)nframes * k->ch * k->ngx;
@@ -989,8 +1009,11 @@ static void resolve_fast(const h2s_ctx* c, const KParams& k, FastParams* F) {
   memset(F, 0, sizeof(*F));
   const h2s_params* p = &c->params;
   const int sh = p->bits_in - 8;
-  const double ys = 1.0 / (219 << sh), yo = -(double)(16 << sh) / (219 << sh);
-  const double cs = 1.0 / (224 << sh), co = -(double)(128 << sh) / (224 << sh);
+  // (a full-range input set, k.full: fill_geometry's constants in double)
+  const double top = (double)((256 << sh) - 1);
+  const double ys = k.full ? 1.0 / top : 1.0 / (219 << sh), yo = k.full ? 0.0 : -(double)(16 << sh) / (219 << sh);
+  const double cs = k.full ? 1.0 / top : 1.0 / (224 << sh);
+  const double co = k.full ? -(double)(128 << sh) / top : -(double)(128 << sh) / (224 << sh);
   const double kr = 0.2627, kb = 0.0593, kg = 1.0 - kr - kb;
   const double mrcr = 2.0 * (1.0 - kr), mgcb = -2.0 * kb * (1.0 - kb) / kg, mgcr = -2.0 * kr * (1.0 - kr) / kg,
                mbcb = 2.0 * (1.0 - kb);
@@ -1016,9 +1039,16 @@ static void resolve_fast(const h2s_ctx* c, const KParams& k, FastParams* F) {
     // E <= Y' + max_c sum |a| * safe_c < PQ_EMAX.  Table forms only (E staged
     // in segment units + 1); the direct HLG form has no exact path
     const bool table = p->transfer_in == H2S_TRC_PQ || k.pipe != h2s::PIPE_LIBPLACEBO;
-    const double safe_c = (double)(112 << sh);
+    // Full range (k.full): every code is legal.  With safe_c at the whole
+    // half-range (128 << sh) the luma bound would fall to Y' < 0.93 and every
+    // bright tile would lose the branch-free body, so the split goes the other
+    // way: the luma bound is set just above Y' = 1 (every luma code passes)
+    // and safe_c is what that leaves, (EMAX - 1e-3 - ymax) / amax = 92.9 % of
+    // the half-range (475 of 512 codes at 10 bits).  Only tiles with chroma
+    // beyond it take the exact-capable body
     const double amax = std::max(std::max(fabs(mrcr), fabs(mgcb) + fabs(mgcr)), fabs(mbcb)) * cs;
-    const double ymax = (double)h2s::PQ_EMAX - amax * safe_c - 1e-3;
+    const double safe_c = k.full ? floor(((double)h2s::PQ_EMAX - 1e-3 - (1.0 + 1e-4)) / amax) : (double)(112 << sh);
+    const double ymax = k.full ? 1.0 + 1e-4 : (double)h2s::PQ_EMAX - amax * safe_c - 1e-3;
     F->safe_c = table ? (float)safe_c : HUGE_VALF;
     F->safe_y = table ? (float)(ymax * h2s::PQ_SEG + 1.0) : HUGE_VALF;
   }
@@ -1249,7 +1279,9 @@ static hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& 
   F.chr_w = k.W;
   F.inv_c56 = 1.0f / F.c56;
   const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
-  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s, k.sub);
+  // (top-left 4:2:0: the SUB 3 instances, h2s_fast_tl.hip / h2s_fast_lp_tl.hip)
+  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s,
+                          k.vco ? 3 : k.sub);
 }
 
 // the generic kernel over a column range of k's frames: every column, or the
@@ -1799,9 +1831,10 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
   // (4:2:0 input: there are no debug instances of the tile kernel for 4:2:2 /
-  // 4:4:4 input, whose planes are the generic kernel's whatever the path)
+  // 4:4:4 input or for a top-left set, whose planes are the generic kernel's
+  // whatever the path; a full-range set changes constants only)
   e = h2s::launch_debug(k, stage, dout, s);
-  if (e == hipSuccess && r.tile() && c->in_fmt.sub == H2S_SUB_420) {
+  if (e == hipSuccess && r.tile() && c->in_fmt.sub == H2S_SUB_420 && !c->in_fmt.vco()) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
       return rc;
@@ -1869,6 +1902,16 @@ int h2s_set_input_subsampling(h2s_ctx* c, int subsampling) {
     return fail(c, H2S_E_INVALID_ARG, "unknown chroma subsampling");
   // (only the arguments of later launches change: nothing queued reads this)
   c->in_fmt.sub = subsampling;
+  return 0;
+}
+
+int h2s_set_input_tags(h2s_ctx* c, int range, int chroma_location) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  if (range != H2S_RANGE_LIMITED && range != H2S_RANGE_FULL) return fail(c, H2S_E_INVALID_ARG, "unknown colour range");
+  if (chroma_location != H2S_CHROMA_LEFT && chroma_location != H2S_CHROMA_TOPLEFT)
+    return fail(c, H2S_E_INVALID_ARG, "unknown chroma location (left and topleft are modelled)");
+  // (only the arguments of later launches change: nothing queued reads these)
+  c->in_fmt.range = range, c->in_fmt.loc = chroma_location;
   return 0;
 }
 

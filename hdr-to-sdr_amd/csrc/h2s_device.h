@@ -106,6 +106,12 @@ struct KParams {
   // 4:2:2, 2 = 4:4:4) and its chroma plane icw x ich (W/2 x H/2, W/2 x H, W x
   // H).  cw, ch, ngx and total above are the output side's, always W/2 x H/2
   int sub, icw, ich;
+  // the input's tags (h2s_set_input_tags).  full: full-range codes, y_scale ..
+  // c_off above are then 1 / (2^b - 1), 0, 1 / (2^b - 1), -2^(b-1) / (2^b - 1)
+  // (the exact path's double forms read the flag).  vco: 4:2:0 chroma rows
+  // co-sited with the even luma rows (top-left): vertical taps (0, 1) on even
+  // rows, (1/2, 1/2) with row cy + 1 on odd ones; 0 whenever sub != 0
+  int full, vco;
 };
 
 constexpr int PIPE_CPU = 1, PIPE_LIBPLACEBO = 2;

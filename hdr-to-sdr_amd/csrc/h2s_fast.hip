@@ -12,6 +12,8 @@ H2S_TILE_EXTERN(0, 0, true)      // h2s_fast_semi.hip: the instances for semi-pl
 H2S_TILE_EXTERN(0, 1, true)      // h2s_fast_lp_semi.hip
 H2S_TILE_EXTERN(0, 0, true, 1)   // h2s_fast_sub422.hip: 4:2:2 input
 H2S_TILE_EXTERN(0, 0, true, 2)   // h2s_fast_sub444.hip: 4:4:4 input
+H2S_TILE_EXTERN(0, 0, true, 3)   // h2s_fast_tl.hip: top-left 4:2:0 input
+H2S_TILE_EXTERN(0, 1, true, 3)   // h2s_fast_lp_tl.hip
 H2S_TILE_EXTERN(1, 0, false)     // h2s_debug.hip: the debug instances
 H2S_TILE_EXTERN(1, 1, false)     // h2s_debug_lp.hip
 H2S_TILE_EXTERN(1, 0, true)      // h2s_debug_semi.hip
@@ -46,7 +48,9 @@ bool fast_supported(int tonemap) { return tonemap >= 4 && tonemap <= 8; }
 // F.dbg_stage: 0 = the product kernel; 1..5 = the chain's debug instance, which
 // also writes that h2s_stage's planes (F.dbg set)
 // sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4: CPU chain product
-// instances only; anything else there is an error, never another kernel)
+// instances only; anything else there is an error, never another kernel), or
+// 3 = 4:2:0 sited top-left (h2s_set_input_tags): either chain's product
+// instances, planar or semi-planar sets; there are no debug instances
 hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub) {
   const long long nt = (long long)F.nbx * F.nby * F.nframes;
   if (nt == 0) return hipSuccess;
@@ -58,6 +62,11 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   const size_t lds = ((size_t)F.eq_n * sizeof(uint16_t) + 15) & ~(size_t)15;
   if (tm == 7 || tm == 8 || lp) desat = 0;
   const bool dbg = F.dbg_stage != 0;
+  if (sub == 3) {
+    if (dbg) return hipErrorInvalidValue;
+    return lp ? launch_tile<0, 1, true, 3>(F, trc, tm, desat, grid, lds, s)
+              : launch_tile<0, 0, true, 3>(F, trc, tm, desat, grid, lds, s);
+  }
   if (sub) {
     if (lp || dbg || F.in_semi || sub > 2) return hipErrorInvalidValue;
     return sub == 1 ? launch_tile<0, 0, true, 1>(F, trc, tm, desat, grid, lds, s)

@@ -49,6 +49,11 @@ __device__ __forceinline__ int ldc(const KParams& P, const uint8_t* row, int x) 
 // 4:2:2, chroma rows 2cy and 2cy+1 of a W/2 x H plane through the horizontal
 // pass alone; 2 = 4:4:4, the pixel's own sample of a W x H plane.  The output
 // side (the work item, the 2x2 reduction, the stores) is 4:2:0 whatever SUB
+// P.vco (launch-uniform; h2s_set_input_tags, 4:2:0 input sited top-left): the
+// vertical taps are (0, 1) on the even luma row and (1/2, 1/2) with row cy + 1
+// on the odd one, in every form (DYN and LPX included); a field (read as four
+// tap weights, no branch in the pixel loop), not a template value, so that no
+// instance is added
 template <int QPT, bool VEC, bool OUT8, bool C444 = false, bool DYN = false, bool LPX = false, int SUB = 0>
 __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   static_assert(SUB == 0 || (!DYN && !LPX), "4:2:2 / 4:4:4 input: CPU chain, static peak");
@@ -163,6 +168,7 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
 
   // ---- per pixel chain, Y'CbCr, quantise ----
   int yo[2][2 * QPT], uo[QPT], vo[QPT];
+  const float vw[4] = {P.vco ? 0.0f : 0.25f, P.vco ? 1.0f : 0.75f, P.vco ? 0.5f : 0.75f, P.vco ? 0.5f : 0.25f};
 #pragma unroll
   for (int k = 0; k < QPT; k++) {
     float cbs[4], crs[4];
@@ -170,8 +176,10 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
     for (int p = 0; p < 4; p++) {
       const int j = p >> 1, x = 2 * k + (p & 1);
       // (SUB: no vertical pass; row j of the loaded pair is the pixel's own)
-      const float cb = SUB ? hu[j][x] : j == 0 ? 0.25f * hu[0][x] + 0.75f * hu[1][x] : 0.75f * hu[1][x] + 0.25f * hu[2][x];
-      const float cr = SUB ? hv[j][x] : j == 0 ? 0.25f * hv[0][x] + 0.75f * hv[1][x] : 0.75f * hv[1][x] + 0.25f * hv[2][x];
+      // (the taps as launch-uniform weights, vw: centre siting 1/4, 3/4 | 3/4, 1/4; top-left 0, 1 | 1/2, 1/2,
+      // where 0 x + 1 y is y exactly)
+      const float cb = SUB ? hu[j][x] : j == 0 ? vw[0] * hu[0][x] + vw[1] * hu[1][x] : vw[2] * hu[1][x] + vw[3] * hu[2][x];
+      const float cr = SUB ? hv[j][x] : j == 0 ? vw[0] * hv[0][x] + vw[1] * hv[1][x] : vw[2] * hv[1][x] + vw[3] * hv[2][x];
       const float yv = (float)ys[j][x] * P.y_scale + P.y_off;
       float r, g, b;
       const int px = 2 * (cx0 + k) + (p & 1), py = 2 * cy + j;
@@ -181,8 +189,9 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
           const double a = lpx_chroma(P, c[i][x >> 1]);
           return (x & 1) ? 0.5 * (a + lpx_chroma(P, c[i][(x >> 1) + 1])) : a;
         };
-        const double cbd = j == 0 ? 0.25 * hx(ccu, 0) + 0.75 * hx(ccu, 1) : 0.75 * hx(ccu, 1) + 0.25 * hx(ccu, 2);
-        const double crd = j == 0 ? 0.25 * hx(ccv, 0) + 0.75 * hx(ccv, 1) : 0.75 * hx(ccv, 1) + 0.25 * hx(ccv, 2);
+        const double wd[4] = {vw[0], vw[1], vw[2], vw[3]};   // (exact in float)
+        const double cbd = j == 0 ? wd[0] * hx(ccu, 0) + wd[1] * hx(ccu, 1) : wd[2] * hx(ccu, 1) + wd[3] * hx(ccu, 2);
+        const double crd = j == 0 ? wd[0] * hx(ccv, 0) + wd[1] * hx(ccv, 1) : wd[2] * hx(ccv, 1) + wd[3] * hx(ccv, 2);
         lpx_chain<4>(P, X, lpx_luma(P, ys[j][x]), cbd, crd, px, py, r, g, b);
       } else {
         chain_px<4>(P, yv, cb, cr, r, g, b, lp_qoff(P, px, py));
@@ -316,6 +325,7 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
   auto up = [&](int plane) -> float {
     if (P.sub) return hpass(plane, y);   // 4:2:2 / 4:4:4: chroma row y, no vertical pass
     const int m = y >> 1;
+    if (P.vco) return !(y & 1) ? hpass(plane, m) : 0.5f * hpass(plane, m) + 0.5f * hpass(plane, m + 1);   // top-left
     if (!(y & 1)) return 0.25f * hpass(plane, m - 1) + 0.75f * hpass(plane, m);
     return 0.75f * hpass(plane, m) + 0.25f * hpass(plane, m + 1);
   };
@@ -333,6 +343,7 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
     };
     auto upd = [&](int plane) -> double {
       const int m = y >> 1;
+      if (P.vco) return !(y & 1) ? hpd(plane, m) : 0.5 * hpd(plane, m) + 0.5 * hpd(plane, m + 1);
       if (!(y & 1)) return 0.25 * hpd(plane, m - 1) + 0.75 * hpd(plane, m);
       return 0.75 * hpd(plane, m) + 0.25 * hpd(plane, m + 1);
     };

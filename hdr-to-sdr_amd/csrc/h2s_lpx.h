@@ -252,11 +252,14 @@ __device__ __forceinline__ void lpx_chain(const KParams& P, const LpX& X, double
 
 // exact normalised samples from integer codes (zimg's limited-range
 // conversion without its float rounding): luma (c - 16 s) / 219 s, chroma
-// (c - 128 s) / 224 s, s = 2^(bits - 8)
+// (c - 128 s) / 224 s, s = 2^(bits - 8); a full-range set (P.full,
+// h2s_set_input_tags): c / (256 s - 1) and (c - 128 s) / (256 s - 1)
 __device__ __forceinline__ double lpx_luma(const KParams& P, int code) {
+  if (P.full) return (double)code / (double)((256 << P.x_sh) - 1);
   return ((double)code - (double)(16 << P.x_sh)) / (double)(219 << P.x_sh);
 }
 __device__ __forceinline__ double lpx_chroma(const KParams& P, int code) {
+  if (P.full) return ((double)code - (double)(128 << P.x_sh)) / (double)((256 << P.x_sh) - 1);
   return ((double)code - (double)(128 << P.x_sh)) / (double)(224 << P.x_sh);
 }
 

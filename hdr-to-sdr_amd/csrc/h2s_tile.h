@@ -1236,6 +1236,12 @@ __device__ __forceinline__ void put_chroma_semi(const FastParams& F, const TileG
 // rows of C444_ST.  The step hands lin_tone the same x8 centred values (exact
 // small integers), so everything after S0 is the 4:2:0 instance's code.  The
 // SUB 0 instances compile to what they were before the parameter existed
+// SUB 3 (h2s_set_input_tags, H2S_CHROMA_TOPLEFT): 4:2:0 input whose chroma rows
+// are co-sited with the even luma rows, product instances of both chains (DBG
+// 0; SEMI, so either side may be semi-planar).  Loads, staging and hrow are the
+// 4:2:0 form's (rows cy0 - 1 .. cy0 + 16, of which row cy0 - 1 is not used);
+// only the step's vertical combine differs: 4 h[cy] on even luma rows,
+// 2 (h[cy] + h[cy + 1]) on odd ones, the same x8 exact integers
 template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false, int SUB = 0>
 // 5 waves per SIMD = the LDS-bound occupancy (5 blocks of ~27.6 KB per CU;
 // 3, 4 and 6 measured slower on the bench content, 6 by 4.5 % in round 3 at
@@ -1253,7 +1259,9 @@ template <int TRC, int TM, int DESAT, int LP, int DBG = 0, bool SEMI = false, in
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TILE_WPE_LP : H2S_TILE_WPE))) void k_tile(
     const FastParams F) {
   static_assert(DBG == 0 || DBG == 1, "the stage is F.dbg_stage, not a template value");
-  static_assert(SUB == 0 || (LP == 0 && DBG == 0), "4:2:2 / 4:4:4 input: CPU chain product instances only");
+  static_assert(SUB == 0 || SUB == 3 || (LP == 0 && DBG == 0), "4:2:2 / 4:4:4 input: CPU chain product instances only");
+  static_assert(SUB != 3 || (DBG == 0 && SEMI), "top-left 4:2:0 input: the SEMI product instances");
+  constexpr bool S420 = SUB == 0 || SUB == 3;   // the input is 4:2:0 (4:2:0 loads and staging)
   constexpr int YST = row_stride<LP>(), HST = YST;
   static_assert(TBH * C422_ST <= (CBH + 2) * HST && TBH * C444_ST <= 2 * (CBH + 2) * HST, "hrow holds the SUB windows");
   __shared__ float yin[TBH * YST];             // luma samples x ys; output codes overwrite them in place
@@ -1327,7 +1335,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   // vertical pass (centre siting): 3 x row cy + row cy-1 (top) / cy+1 (bottom)
   const float* h0 = hrow[0] + (qy + 1) * HST + xl;
   const float* h1 = hrow[1] + (qy + 1) * HST + xl;
-  const int hb = pyl ? HST : -HST;
+  // (SUB 3, rows co-sited with the even luma row: row cy again (even luma rows) / cy+1 (odd))
+  const int hb = SUB == 3 ? (pyl ? HST : 0) : (pyl ? HST : -HST);
   // SUB 1: the pixel's own chroma row, sample xl >> 1 and (odd columns) the one right of it
   const float* c0 = hrow[0] + yl * C422_ST + (xl >> 1);
   const float* c1 = hrow[1] + yl * C422_ST + (xl >> 1);
@@ -1425,8 +1434,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
             const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
             H2S_MARK("S0 step: staged Y, vertical chroma");
             const float ybs = ybase[oy];
-            const float U = fmaf(3.0f, h0[oh], h0[oh + hb]);   // x8 upsampled, centred, exact
-            const float V = fmaf(3.0f, h1[oh], h1[oh + hb]);
+            // x8 upsampled, centred, exact (SUB 3: 4 h[cy], or 2 (h[cy] + h[cy+1]))
+            const float U = SUB == 3 ? 2.0f * (h0[oh] + h0[oh + hb]) : fmaf(3.0f, h0[oh], h0[oh + hb]);
+            const float V = SUB == 3 ? 2.0f * (h1[oh] + h1[oh + hb]) : fmaf(3.0f, h1[oh], h1[oh + hb]);
             float r, gg, bl;
             lin_tone<TRC, TM, DESAT, LP, 0, FB>(F, cv, pq_lds, pqi_lds, K, ybs, U, V, [](float, float, float) {},
                                                  r, gg, bl);
@@ -1462,6 +1472,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       } else if constexpr (SUB == 2) {   // 8 (code - mid)
         const int oc = 8 * (s >> 1) * C444_ST + 8 * (s & 1);
         U = 8.0f * (float)s0[oc], V = 8.0f * (float)s1[oc];
+      } else if constexpr (SUB == 3) {   // 4 h[cy] (even luma rows), or 2 (h[cy] + h[cy+1])
+        U = 2.0f * (h0[oh] + h0[oh + hb]), V = 2.0f * (h1[oh] + h1[oh + hb]);
       } else {
         U = fmaf(3.0f, h0[oh], h0[oh + hb]);   // x8 upsampled, centred, exact
         V = fmaf(3.0f, h1[oh], h1[oh + hb]);
@@ -1490,7 +1502,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       // semi-planar: the code sits in each 16-bit word's high bits; both
       // halves of a pair move down together and the mask (always set then)
       // clears what crossed from the high half, and the word's low junk bits
-      if constexpr (SEMI && SUB == 0) {
+      if constexpr (SEMI && S420) {
         if (F.in_sh) {
           shift_in(cur.ya), shift_in(cur.ua);
           cur.uh >>= F.in_sh;
@@ -1599,7 +1611,8 @@ hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 gri
 // launch_tile's arguments <DBG, LPI, SEMI[, SUB]>: each chain's planar and
 // SEMI instances in a translation unit of their own, and one per SUB for the
 // 4:2:2 / 4:4:4 input instances <0, 0, true, SUB> (the CPU chain's product
-// kernels with the output side's layout branches)
+// kernels with the output side's layout branches) and for each chain's
+// top-left 4:2:0 instances <0, LPI, true, 3>
 #define H2S_TILE_EXTERN(...) \
   extern template hipError_t launch_tile<__VA_ARGS__>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 #define H2S_TILE_INSTANCE(...) \

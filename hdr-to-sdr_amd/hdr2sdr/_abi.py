@@ -31,6 +31,10 @@ LAYOUT_PLANAR, LAYOUT_SEMI = 0, 1   # enum h2s_layout (h2s_set_frame_layout)
 LAYOUTS = {'planar': LAYOUT_PLANAR, 'semi': LAYOUT_SEMI}
 SUB_420, SUB_422, SUB_444 = 0, 1, 2   # enum h2s_subsampling (h2s_set_input_subsampling)
 SUBSAMPLINGS = {'420': SUB_420, '422': SUB_422, '444': SUB_444}
+RANGE_LIMITED, RANGE_FULL = 0, 1       # enum h2s_range (h2s_set_input_tags)
+CHROMA_LEFT, CHROMA_TOPLEFT = 0, 1     # enum h2s_chroma_loc
+COLOR_RANGES = {'tv': RANGE_LIMITED, 'pc': RANGE_FULL}   # ffprobe's color_range / chroma_location values
+CHROMA_LOCATIONS = {'left': CHROMA_LEFT, 'topleft': CHROMA_TOPLEFT}
 STAGE_LINEAR, STAGE_TONEMAP, STAGE_GAMMA, STAGE_LUT, STAGE_YUV = 1, 2, 3, 4, 5
 CHROMA_BOX, CHROMA_BICUBIC = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1
@@ -60,7 +64,7 @@ EXPORTS = (
     'h2s_debug_float', 'h2s_cube_generate', 'h2s_cube_format', 'h2s_cube_parse',
     'h2s_kernel_ms', 'h2s_set_timing', 'h2s_preview_size', 'h2s_preview_rgb24', 'h2s_preview_rgb24_batch', 'h2s_peak_reset',
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
-    'h2s_set_frame_layout', 'h2s_set_input_subsampling',
+    'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
 )
 
 
@@ -186,6 +190,7 @@ def lib() -> ctypes.CDLL:
         'h2s_query_path': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SFrames)]),
         'h2s_set_frame_layout': (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_int]),
         'h2s_set_input_subsampling': (ctypes.c_int, [c_ctx, ctypes.c_int]),
+        'h2s_set_input_tags': (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_int]),
         'h2s_preview_size': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         'h2s_preview_rgb24': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.c_void_p, ctypes.c_int64,

@@ -35,6 +35,7 @@ class Tonemapper:
         self.lut_size = 0
         self._layouts = ('planar', 'planar')   # what the context last got (h2s_set_frame_layout)
         self._subsampling = '420'              # ... (h2s_set_input_subsampling)
+        self._tags = ('tv', 'left')            # ... (h2s_set_input_tags)
         if params is not None:
             self.set_params(params)
         if lut is not None:
@@ -118,11 +119,27 @@ class Tonemapper:
             self._check(self._L.h2s_set_input_subsampling(self._ctx, _abi.SUBSAMPLINGS[subsampling]))
             self._subsampling = subsampling
 
+    def set_input_tags(self, color_range: str = 'tv', chroma_location: str = 'left') -> None:
+        """The source tags later calls read their source batch with
+        (color_range 'tv' | 'pc', chroma_location 'left' | 'topleft';
+        h2s_set_input_tags).  process, query_path, debug_float and peak_stats
+        set them from their source batch, so a tag never sticks from one batch
+        to the next and callers of those never need to."""
+        if color_range not in _abi.COLOR_RANGES:
+            raise ValueError(f"color_range must be 'tv' or 'pc', got {color_range!r}")
+        if chroma_location not in _abi.CHROMA_LOCATIONS:
+            raise ValueError(f"chroma_location must be 'left' or 'topleft', got {chroma_location!r}")
+        if (color_range, chroma_location) != self._tags:
+            self._check(self._L.h2s_set_input_tags(self._ctx, _abi.COLOR_RANGES[color_range],
+                                                   _abi.CHROMA_LOCATIONS[chroma_location]))
+            self._tags = (color_range, chroma_location)
+
     def _use_layouts(self, src: FrameBatch, dst: 'FrameBatch | None' = None) -> None:
         # (a call without a destination batch leaves the output side as it is)
         self.set_frame_layout(getattr(src, 'layout', 'planar'),
                               self._layouts[1] if dst is None else getattr(dst, 'layout', 'planar'))
         self.set_input_subsampling(getattr(src, 'subsampling', '420'))
+        self.set_input_tags(getattr(src, 'color_range', 'tv'), getattr(src, 'chroma_location', 'left'))
         if dst is not None and getattr(dst, 'subsampling', '420') != '420':
             raise ValueError('the output side is 4:2:0 (destination batch subsampling must be 420)')
 

@@ -25,6 +25,13 @@ Source batches may also be planar 4:2:2 or 4:4:4 (``subsampling='422'`` /
 planes of H x W/2 or H x W samples: W * H * 2 or W * H * 3 samples per frame.
 The kernels read them at their own chroma resolution
 (h2s_set_input_subsampling); the output side is always 4:2:0.
+
+A source batch also carries two tags of its stream (``color_range`` 'tv' |
+'pc', ``chroma_location`` 'left' | 'topleft': ffprobe's fields of those names),
+which the kernels honour when they read it (h2s_set_input_tags): full-range
+codes, and 4:2:0 chroma rows co-sited with the even luma rows.  They describe
+how the samples are to be read and change nothing about the buffer; on a
+destination batch they are ignored (the output is limited range, left-sited).
 """
 from __future__ import annotations
 
@@ -39,6 +46,8 @@ from . import _abi
 
 LAYOUTS = ('planar', 'semi')
 SUBSAMPLINGS = ('420', '422', '444')
+COLOR_RANGES = ('tv', 'pc')
+CHROMA_LOCATIONS = ('left', 'topleft')
 # chroma plane = (width >> cxs) x (height >> cys) samples
 _CHROMA_SHIFTS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}
 
@@ -70,14 +79,26 @@ class FrameBatch:
     bits: int
     layout: str = 'planar'
     subsampling: str = '420'
+    color_range: str = 'tv'
+    chroma_location: str = 'left'
 
     def __post_init__(self):
+        if self.color_range not in COLOR_RANGES:
+            raise ValueError(f"color_range must be 'tv' or 'pc', got {self.color_range!r}")
+        if self.chroma_location not in CHROMA_LOCATIONS:
+            raise ValueError(f"chroma_location must be 'left' or 'topleft', got {self.chroma_location!r} "
+                             '(other chroma locations are not modelled)')
         if self.layout not in LAYOUTS:
             raise ValueError(f"layout must be 'planar' or 'semi', got {self.layout!r}")
         if self.subsampling not in SUBSAMPLINGS:
             raise ValueError(f"subsampling must be '420', '422' or '444', got {self.subsampling!r}")
         if self.subsampling != '420' and self.layout == 'semi':
             raise ValueError('4:2:2 / 4:4:4 batches are planar only (no p210 / p410)')
+
+    def _like(self, buf: Any, layout: 'str | None' = None) -> 'FrameBatch':
+        """A batch over ``buf`` with this batch's geometry, form and tags."""
+        return FrameBatch(buf, self.width, self.height, self.bits, self.layout if layout is None else layout,
+                          self.subsampling, self.color_range, self.chroma_location)
 
     # ---- constructors ---------------------------------------------------
     @staticmethod
@@ -93,22 +114,25 @@ class FrameBatch:
 
     @classmethod
     def empty_torch(cls, nframes: int, width: int, height: int, bits: int, device: Any,
-                    layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
+                    layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
+                    chroma_location: str = 'left') -> 'FrameBatch':
         import torch
         dt = torch.uint8 if bits == 8 else torch.int16
         return cls(torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, device=device),
-                   width, height, bits, layout, subsampling)
+                   width, height, bits, layout, subsampling, color_range, chroma_location)
 
     @classmethod
     def empty_numpy(cls, nframes: int, width: int, height: int, bits: int,
-                    layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
+                    layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
+                    chroma_location: str = 'left') -> 'FrameBatch':
         dt = np.uint8 if bits == 8 else np.uint16
         return cls(np.zeros(cls._shape(nframes, width, height, bits, subsampling), dtype=dt), width, height, bits,
-                   layout, subsampling)
+                   layout, subsampling, color_range, chroma_location)
 
     @classmethod
     def empty_pinned(cls, nframes: int, width: int, height: int, bits: int,
-                     layout: str = 'planar', subsampling: str = '420') -> 'FrameBatch':
+                     layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
+                     chroma_location: str = 'left') -> 'FrameBatch':
         """Host batch in page-locked memory (DMA-able without a bounce copy:
         the host-buffer path of h2s_process then runs at PCIe speed). Falls
         back to pageable numpy memory when no GPU runtime is present."""
@@ -118,20 +142,20 @@ class FrameBatch:
                 dt = torch.uint8 if bits == 8 else torch.int16
                 t = torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, pin_memory=True)
                 a = t.numpy() if bits == 8 else t.numpy().view(np.uint16)
-                fb = cls(a, width, height, bits, layout, subsampling)
+                fb = cls(a, width, height, bits, layout, subsampling, color_range, chroma_location)
                 fb._pin = t          # keep the pinned allocation alive
                 return fb
         except (ImportError, RuntimeError):
             pass
-        return cls.empty_numpy(nframes, width, height, bits, layout, subsampling)
+        return cls.empty_numpy(nframes, width, height, bits, layout, subsampling, color_range, chroma_location)
 
     @classmethod
     def from_planes(cls, y: np.ndarray, u: np.ndarray, v: np.ndarray, bits: int,
-                    subsampling: str = '420') -> 'FrameBatch':
+                    subsampling: str = '420', color_range: str = 'tv', chroma_location: str = 'left') -> 'FrameBatch':
         """Pack [F,H,W] / [F,H/2,W/2] numpy planes into a batch (4:2:2: U, V
         [F,H,W/2]; 4:4:4: [F,H,W])."""
         f, h, w = y.shape
-        fb = cls.empty_numpy(f, w, h, bits, 'planar', subsampling)
+        fb = cls.empty_numpy(f, w, h, bits, 'planar', subsampling, color_range, chroma_location)
         fb.y[...] = y
         fb.u[...] = u
         fb.v[...] = v
@@ -185,18 +209,17 @@ class FrameBatch:
         a = self.buf.detach().cpu().numpy()
         if self.bits != 8:
             a = a.view(np.uint16)
-        return FrameBatch(a, self.width, self.height, self.bits, self.layout, self.subsampling)
+        return self._like(a)
 
     def to_torch(self, device: Any) -> 'FrameBatch':
         import torch
         if self.is_torch:
-            return FrameBatch(self.buf.to(device), self.width, self.height, self.bits, self.layout, self.subsampling)
+            return self._like(self.buf.to(device))
         a = self.buf if self.bits == 8 else self.buf.view(np.int16)
-        return FrameBatch(torch.from_numpy(np.ascontiguousarray(a)).to(device), self.width, self.height, self.bits,
-                          self.layout, self.subsampling)
+        return self._like(torch.from_numpy(np.ascontiguousarray(a)).to(device))
 
     def slice(self, start: int, stop: int) -> 'FrameBatch':
-        return FrameBatch(self.buf[start:stop], self.width, self.height, self.bits, self.layout, self.subsampling)
+        return self._like(self.buf[start:stop])
 
     def to_layout(self, layout: str) -> 'FrameBatch':
         """A copy of the batch in ``layout`` (the batch itself when it already
@@ -214,7 +237,7 @@ class FrameBatch:
         sh = 0 if self.bits == 8 else 16 - self.bits
         if self.is_torch:
             import torch
-            dst = FrameBatch(torch.empty_like(self.buf), self.width, self.height, self.bits, layout)
+            dst = self._like(torch.empty_like(self.buf), layout)
             # (int16 storage: the codes move as unsigned 16-bit words)
             def up(x):
                 if not sh:
@@ -225,7 +248,7 @@ class FrameBatch:
             def down(x):
                 return ((x.to(torch.int32) & 0xFFFF) >> sh).to(torch.int16) if sh else x
         else:
-            dst = FrameBatch(np.empty_like(self.buf), self.width, self.height, self.bits, layout)
+            dst = self._like(np.empty_like(self.buf), layout)
 
             def up(x):
                 return (x.astype(np.uint32) << sh).astype(self.buf.dtype) if sh else x

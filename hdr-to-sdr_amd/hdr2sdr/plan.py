@@ -12,7 +12,9 @@ encode and mux. The tone-map chain moves onto the GPU between two pipes:
              (or p010le / p012le, and nv12 / p010le / p012le on the encode
              pipe: the semi-planar layouts, ``in_layout`` / ``out_layout``;
              or yuv422p1Xle / yuv444p1Xle for such a source on the CPU chain,
-             ``in_subsampling``)
+             ``in_subsampling``; the source's own family either way, so a
+             full-range or top-left source's codes cross the pipe untouched and
+             the kernels honour the tags, ``in_range`` / ``in_chroma_location``)
     libh2s:  h2s_process() on batches of frames
     encode:  ffmpeg -f rawvideo … -i - -i IN <every non-filter option build() chose>
 
@@ -49,6 +51,10 @@ OUT_PIX_FMT_BITS = {'yuv420p': 8, 'yuv420p10le': 10, 'p010le': 10, 'yuv420p12le'
 # setparams=color_primaries=bt709:color_trc=bt709:colorspace=bt709 (src/utils.py:40)
 # on frames that leave zscale r=tv: as output tags on the encode side
 BT709_TAGS = ['-color_primaries', 'bt709', '-color_trc', 'bt709', '-colorspace', 'bt709', '-color_range', 'tv']
+# ffprobe color_range / chroma_location -> in_range / in_chroma_location 'auto'
+# (absent, 'unknown' and 'unspecified' are the defaults: tv, left)
+SOURCE_RANGE = {'': 'tv', 'unknown': 'tv', 'unspecified': 'tv', 'tv': 'tv', 'pc': 'pc'}
+SOURCE_CHROMA_LOCATION = {'': 'left', 'unknown': 'left', 'unspecified': 'left', 'left': 'left', 'topleft': 'topleft'}
 TRANSFERS = {'smpte2084': 'smpte2084', 'arib-std-b67': 'arib-std-b67', '': 'smpte2084'}
 
 
@@ -69,6 +75,9 @@ class PipePlan:
     layout: str = 'planar'
     # chroma subsampling on the decode pipe ('420' | '422' | '444')
     in_subsampling: str = '420'
+    # the source's tags, handed to every source batch ('tv' | 'pc', 'left' | 'topleft')
+    in_range: str = 'tv'
+    in_chroma_location: str = 'left'
 
     @property
     def frame_bytes_in(self) -> int:
@@ -89,7 +98,8 @@ def _remap_input(spec: str) -> str:
 
 def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[str, Any] | None' = None,
                    mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar',
-                   in_subsampling: str = '420') -> PipePlan:
+                   in_subsampling: str = '420', in_range: str = 'tv',
+                   in_chroma_location: str = 'left') -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
 
     in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
@@ -112,6 +122,19 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     whatever is asked: the reference uploads ``format=p010`` there
     (src/utils.py:430-431), so swscale's 4:2:0 is what libplacebo sees.
     Planar input only.
+
+    in_range ('tv' | 'pc' | 'auto') and in_chroma_location ('left' | 'topleft'
+    | 'auto'): the source's colour range and 4:2:0 chroma siting, which the
+    reference's chains take from the decoded frame (zscale has no ``rin=``,
+    vf_libplacebo reads the AVFrame) and the kernels honour
+    (h2s_set_input_tags); both apply to both pipelines.  The defaults are the
+    untagged behaviour.  'auto' reads ``properties.get('color_range')`` /
+    ``properties.get('chroma_location')`` (ffprobe's stream fields; the
+    reference's ``get_video_properties`` dict does not carry them): absent,
+    'unknown' or 'unspecified' is 'tv' / 'left'; a chroma location other than
+    left / topleft (center, top, bottomleft, bottom) is not modelled and raises
+    ValueError.  The decode argv does not change: the pipe's ``-pix_fmt`` is
+    the source's own family, so the codes pass through as they are.
 
     properties: the reference's ``get_video_properties`` dict
     (src/utils.py:1040-1058): width, height, bit_depth, color_transfer.
@@ -190,6 +213,20 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
         in_subsampling = '420'     # format=p010,hwupload: the reference's own 4:2:0
     if in_subsampling != '420' and in_layout == 'semi':
         raise ValueError('4:2:2 / 4:4:4 decode pipes are planar only (no p210 / p410)')
+    if in_range not in ('tv', 'pc', 'auto'):
+        raise ValueError(f"in_range must be 'tv', 'pc' or 'auto', got {in_range!r}")
+    if in_chroma_location not in ('left', 'topleft', 'auto'):
+        raise ValueError(f"in_chroma_location must be 'left', 'topleft' or 'auto', got {in_chroma_location!r}")
+    if in_range == 'auto':
+        tag = str(properties.get('color_range') or '')
+        if tag not in SOURCE_RANGE:
+            raise ValueError(f'unsupported source color_range {tag!r} (expected tv or pc)')
+        in_range = SOURCE_RANGE[tag]
+    if in_chroma_location == 'auto':
+        tag = str(properties.get('chroma_location') or '')
+        if tag not in SOURCE_CHROMA_LOCATION:
+            raise ValueError(f'source chroma_location {tag!r} is not modelled (left and topleft are)')
+        in_chroma_location = SOURCE_CHROMA_LOCATION[tag]
     if out_layout == 'auto':
         out_layout = 'semi' if enc_pix_fmt == 'p010le' else 'planar'
     pipe_in = (PIPE_PIX_FMT_SEMI if in_layout == 'semi' else PIPE_PIX_FMT)[bits_in]
@@ -202,7 +239,8 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
               '-r', fps, '-i', '-', '-i', input_path, '-map', '0:v:0'] + encode_opts
     return PipePlan(decode=decode, encode=encode, params=params, lut_path=lut_path, width=W, height=H,
                     input_path=input_path, output_path=output_path, reference_argv=argv,
-                    in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling)
+                    in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling,
+                    in_range=in_range, in_chroma_location=in_chroma_location)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -240,7 +278,7 @@ class H2SProcess:
         # `depth` input slots let the decoder run ahead while the GPU stage
         # and the encoder work on earlier batches.
         self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout,
-                                             plan.in_subsampling)
+                                             plan.in_subsampling, plan.in_range, plan.in_chroma_location)
                      for _ in range(max(1, int(depth)))]
         self._dst = FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_out, plan.layout)
         self._free: 'queue.Queue[Optional[int]]' = queue.Queue()

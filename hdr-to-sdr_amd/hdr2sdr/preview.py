@@ -174,9 +174,10 @@ class Previewer:
         if isinstance(frames, FrameBatch):
             return self._run(frames, width, height, gamma)
         out: 'list[np.ndarray | None]' = [None] * len(frames)
-        groups: 'dict[tuple[int, int, int, bool, Any, str, str], list[int]]' = {}
+        groups: 'dict[tuple, list[int]]' = {}
         for i, f in enumerate(frames):
-            key = (f.width, f.height, f.bits, f.is_torch, getattr(f.buf, 'device', None), f.layout, f.subsampling)
+            key = (f.width, f.height, f.bits, f.is_torch, getattr(f.buf, 'device', None), f.layout, f.subsampling,
+                   f.color_range, f.chroma_location)
             groups.setdefault(key, []).append(i)
         for idx in groups.values():
             firsts = [frames[i] if frames[i].nframes == 1 else frames[i].slice(0, 1) for i in idx]
@@ -185,8 +186,7 @@ class Previewer:
                 buf = torch.cat([f.buf for f in firsts])
             else:
                 buf = np.concatenate([np.asarray(f.buf) for f in firsts])
-            batch = FrameBatch(buf, firsts[0].width, firsts[0].height, firsts[0].bits, firsts[0].layout,
-                               firsts[0].subsampling)
+            batch = firsts[0]._like(buf)
             for i, img in zip(idx, self._run(batch, width, height, gamma)):
                 out[i] = img
         return out   # type: ignore[return-value]
@@ -214,7 +214,7 @@ class Previewer:
         ow, oh = self.out_size(frames.width, frames.height, width, height)
         n = frames.nframes
         out = np.empty((n, oh, ow, 3), dtype=np.uint8)
-        # (semi-planar / 4:2:2 / 4:4:4 input through the context's settings; the RGB output has none)
+        # (semi-planar / 4:2:2 / 4:4:4 / tagged input through the context's settings; the RGB output has none)
         self._tm._use_layouts(frames)
         d = frames.descriptor()
         L = _abi.lib()

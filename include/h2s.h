@@ -61,7 +61,8 @@ extern "C" {
  *      exact path computes stages 1-3 in double precision (see below).
  * Added within 3.4, with no change of either number: h2s_set_frame_layout
  * (semi-planar nv12 / p010le / p012le frame sets); h2s_set_input_subsampling
- * (4:2:2 / 4:4:4 planar input on the CPU chain).  No struct, signature or
+ * (4:2:2 / 4:4:4 planar input on the CPU chain); h2s_set_input_tags (a
+ * source's full-range and top-left chroma tags).  No struct, signature or
  * default behaviour changes, so the symbol's presence in the loaded library
  * is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -128,6 +129,13 @@ enum h2s_layout { H2S_LAYOUT_PLANAR = 0, H2S_LAYOUT_SEMI = 1 };
 /* Chroma subsampling of an input frame set (h2s_set_input_subsampling).  The
  * output side is always 4:2:0. */
 enum h2s_subsampling { H2S_SUB_420 = 0, H2S_SUB_422 = 1, H2S_SUB_444 = 2 };
+
+/* Source tags of an input frame set (h2s_set_input_tags): the colour range of
+ * its codes (ffprobe color_range tv / pc) and where its 4:2:0 chroma samples
+ * sit (chroma_location left / topleft, HEVC chroma_sample_loc_type 0 / 2).
+ * The output side is always limited range. */
+enum h2s_range { H2S_RANGE_LIMITED = 0, H2S_RANGE_FULL = 1 };
+enum h2s_chroma_loc { H2S_CHROMA_LEFT = 0, H2S_CHROMA_TOPLEFT = 1 };
 
 /* Debug stages for h2s_debug_float: three float planes per pixel.
  * 1..4: R, G, B after the stage.  5: the quantiser's inputs, before rounding:
@@ -404,7 +412,9 @@ int h2s_process(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out,
  * planes are a per-frame check of the arithmetic and leave that state
  * untouched.  With 4:2:2 / 4:4:4 input (h2s_set_input_subsampling) the planes
  * are the generic kernel's whatever h2s_query_path says: the tile kernel has
- * no debug instances for those inputs.  Synchronous. */
+ * no debug instances for those inputs; the same holds for a top-left 4:2:0
+ * set (h2s_set_input_tags), while a full-range set changes constants only and
+ * keeps the tile kernel's debug instances.  Synchronous. */
 int h2s_debug_float(h2s_ctx *ctx, const h2s_frames *in, int stage,
                     float *out_rgb, int out_location, void *hip_stream);
 
@@ -446,6 +456,31 @@ int h2s_set_frame_layout(h2s_ctx *ctx, int in_layout, int out_layout);
  *     peak_detect too): the reference uploads format=p010 there, i.e. 4:2:0;
  *   - h2s_peak_stats. */
 int h2s_set_input_subsampling(h2s_ctx *ctx, int subsampling);
+
+/* ---- input source tags (enum h2s_range, enum h2s_chroma_loc; default
+ * LIMITED, LEFT) ------------------------------------------------------------
+ * How every later call on the context interprets the codes and the chroma
+ * siting of its `in` frames: h2s_process (device and host-resident sets),
+ * h2s_query_path, h2s_debug_float, h2s_peak_stats and h2s_preview_rgb24 /
+ * _batch.  The reference's chains honour both tags of the decoded frame
+ * (zscale=t=linear has no rin=, so zimg takes the range from the frame;
+ * vf_libplacebo reads the AVFrame), so both apply to both pipelines, with
+ * peak_detect, and to planar and semi-planar input.  Model ([EXT], unpinned
+ * like the rest of S1), for input depth b:
+ *   H2S_RANGE_FULL: Y' = code / (2^b - 1), Cb, Cr = (code - 2^(b-1)) /
+ *     (2^b - 1) (zimg's full-range integer to float conversion; every code is
+ *     legal).  Nothing after S1's normalisation changes: the output stays
+ *     BT.709 limited range.
+ *   H2S_CHROMA_TOPLEFT (4:2:0 input): the horizontal pass is the left-sited
+ *     one (C[2k] = c[k], C[2k+1] = c[k]/2 + c[k+1]/2); vertically the chroma
+ *     row is co-sited with the even luma row: C[2m] = c[m], C[2m+1] = c[m]/2 +
+ *     c[m+1]/2, row height/2 by params.chroma_edge exactly as column width/2
+ *     (no row above the plane is read).  With 4:2:2 / 4:4:4 input there is no
+ *     vertical pass: the tag is accepted and has no effect.
+ * Other chroma locations (center, top, bottomleft, bottom) are not modelled.
+ * Only the arguments of later launches change, so the call does not wait for
+ * queued work.  An unknown value or a NULL ctx is H2S_E_INVALID_ARG. */
+int h2s_set_input_tags(h2s_ctx *ctx, int range, int chroma_location);
 
 /* ---- dynamic peak (params.peak_detect, BT.2390 / spline) -----------------
  * h2s_peak_reset: forget the smoothing state (a new sequence / scene cut).
