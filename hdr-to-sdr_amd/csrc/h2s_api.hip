@@ -16,6 +16,7 @@
 #include "../../include/h2s.h"
 #include "h2s_device.h"
 #include "h2s_peak.h"
+#include "h2s_srcprev.h"
 
 namespace h2s {
 enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2s_kernels.hip defines it
@@ -1966,9 +1967,10 @@ int resize_taps(int src, int dst, std::vector<float>* w, std::vector<int>* start
   for (int o = 0; o < dst; o++) {
     const double c = (o + 0.5) * scale - 0.5;
     const int s0 = (int)floor(c - 2.0 * fw) + 1;
-    double sum = 0.0, tmp[64];
-    for (int i = 0; i < T && i < 64; i++) sum += (tmp[i] = bicubic((s0 + i - c) / fw));
-    for (int i = 0; i < T && i < 64; i++) (*w)[(size_t)o * T + i] = (float)(tmp[i] / sum);
+    // (T <= 49 at the ratio limit of 12; a 4:4:4 source pane's chroma columns reach 24, T = 97)
+    double sum = 0.0, tmp[128];
+    for (int i = 0; i < T && i < 128; i++) sum += (tmp[i] = bicubic((s0 + i - c) / fw));
+    for (int i = 0; i < T && i < 128; i++) (*w)[(size_t)o * T + i] = (float)(tmp[i] / sum);
     (*start)[o] = s0;
   }
   return T;
@@ -2140,6 +2142,121 @@ int h2s_preview_rgb24(h2s_ctx* c, const h2s_frames* in, uint8_t* rgb, int64_t rg
                       double display_gamma, int rgb_location, void* hip_stream) {
   return h2s_preview_rgb24_batch(c, in, 1, rgb, rgb_linesize, rgb_linesize * (int64_t)out_h, out_w, out_h,
                                  display_gamma, rgb_location, hip_stream);
+}
+
+// The source pane (extract_frame / extract_frames_batch, src/utils.py:827-859,
+// :629-665): the frames as decoded, resized and matrixed by k_source_rgb24 in
+// one launch.  Of the context it reads the input Format alone: no params, LUT,
+// option or peak state, and it leaves all of them as they are
+int h2s_preview_source_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8_t* rgb, int64_t rgb_linesize,
+                                   int64_t rgb_frame_pitch, int out_w, int out_h, int matrix, int rgb_model,
+                                   int rgb_location, void* hip_stream) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  if (nframes < 1) return fail(c, H2S_E_INVALID_ARG, "nframes must be >= 1");
+  if (!rgb || out_w <= 0 || out_h <= 0 || rgb_linesize < 3LL * out_w ||
+      (nframes > 1 && rgb_frame_pitch < rgb_linesize * out_h))
+    return fail(c, H2S_E_INVALID_ARG, "bad RGB output geometry");
+  // (Kr, Kb) of enum h2s_src_matrix
+  static const double kKrKb[3][2] = {{0.2627, 0.0593}, {0.2126, 0.0722}, {0.299, 0.114}};
+  if (matrix < H2S_SRC_MATRIX_BT2020NC || matrix > H2S_SRC_MATRIX_BT601)
+    return fail(c, H2S_E_INVALID_ARG, "unknown source matrix");
+  if (rgb_model != H2S_SRC_RGB_TRUNC16 && rgb_model != H2S_SRC_RGB_ROUND8)
+    return fail(c, H2S_E_INVALID_ARG, "unknown source rgb model");
+  if (!in) return fail(c, H2S_E_INVALID_ARG, "input frames is NULL");
+  if (in->bits != 10 && in->bits != 12)
+    return fail(c, H2S_E_INVALID_ARG, "the source pane reads 10- or 12-bit frames");
+  const Format fmt = c->in_fmt;
+  if (fmt.sub != H2S_SUB_420 && fmt.semi())
+    return fail(c, H2S_E_UNSUPPORTED, "4:2:2 / 4:4:4 input is planar only (semi-planar p210 / p410 input is not supported)");
+  int rc = check_frames(c, in, in->bits, "input", fmt);
+  if (rc) return rc;
+  const int W = in->width, H = in->height, bits = in->bits;
+  const bool scale = out_w != W || out_h != H;
+  if (scale && (out_w > 4 * 8192 || out_h > 4 * 8192 || (double)W / out_w > 12.0 || (double)H / out_h > 12.0))
+    return fail(c, H2S_E_UNSUPPORTED, "preview resize ratio out of range");
+  DeviceGuard g(c->device);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int cw = W >> fmt.cxs(), ch = H >> fmt.cys(), ow2 = (out_w + 1) / 2;
+  // tap tables, one upload each: weights wx | wy | wcx | wcy, first taps sx | sy | scx | scy
+  std::vector<float> wt[4];
+  std::vector<int> st[4];
+  int T[4] = {0, 0, 0, 0};
+  if (scale) {
+    T[0] = resize_taps(W, out_w, &wt[0], &st[0]);
+    T[1] = resize_taps(H, out_h, &wt[1], &st[1]);
+  }
+  T[2] = resize_taps(cw, ow2, &wt[2], &st[2]);
+  T[3] = resize_taps(ch, out_h, &wt[3], &st[3]);
+  std::vector<float> wall;
+  std::vector<int> sall;
+  size_t woff[4], soff[4];
+  for (int i = 0; i < 4; i++) {
+    woff[i] = wall.size(), soff[i] = sall.size();
+    wall.insert(wall.end(), wt[i].begin(), wt[i].end());
+    sall.insert(sall.end(), st[i].begin(), st[i].end());
+  }
+  // scratch: a host set's tight device copy, the tap tables, the RGB staging of a host output
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t n = (size_t)nframes;
+  const bool host_in = in->location == H2S_LOC_HOST, host_out = rgb_location == H2S_LOC_HOST;
+  const size_t in_b = host_in ? al(frame_bytes(in, fmt) * n) : 0;
+  const size_t w_b = al(wall.size() * 4), s_b = al(sall.size() * 4);
+  const size_t rgb_b = host_out ? al((size_t)out_w * 3 * out_h * n) : 0;
+  const size_t need = in_b + w_b + s_b + rgb_b;
+  if (need > c->d_prev.cap && c->d_prev) {
+    // a previous preview's kernels may still read the old scratch
+    drain_launches(c);
+    hipStreamSynchronize(s);
+  }
+  if ((rc = c->d_prev.reserve(c, need, "preview scratch"))) return rc;
+  uint8_t* base = c->d_prev;
+  float* dw = (float*)(base + in_b);
+  int* ds = (int*)(base + in_b + w_b);
+  const h2s_frames din = device_view(in, base, fmt);
+  KParams k{};  // the source set as the conversion kernels bind it
+  fill_geometry(&k, &din, nullptr, nframes, fmt, PLANAR_420);
+  h2s::SrcPreviewParams P{};
+  for (int p = 0; p < 3; p++) P.in[p] = k.in[p], P.ls[p] = k.in_ls[p], P.fp[p] = k.in_fp[p];
+  P.cstep = k.in_cstep, P.sh = k.in_sh, P.mask = (1 << bits) - 1;
+  P.W = W, P.H = H, P.cw = k.icw, P.ch = k.ich;
+  P.ow = out_w, P.oh = out_h, P.ow2 = ow2;
+  P.rgb = host_out ? base + in_b + w_b + s_b : rgb;
+  P.rls = host_out ? 3LL * out_w : rgb_linesize;
+  P.rfp = host_out ? 3LL * out_w * out_h : rgb_frame_pitch;
+  P.identity = scale ? 0 : 1;
+  P.Tx = T[0], P.Ty = T[1], P.Tcx = T[2], P.Tcy = T[3];
+  P.wx = dw + woff[0], P.wy = dw + woff[1], P.wcx = dw + woff[2], P.wcy = dw + woff[3];
+  P.sx = ds + soff[0], P.sy = ds + soff[1], P.scx = ds + soff[2], P.scy = ds + soff[3];
+  const double sc = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
+  P.y_off = fmt.full() ? 0 : 16 << (bits - 8), P.mid = 1 << (bits - 1);
+  P.y_inv = (float)(1.0 / (fmt.full() ? top : 219.0 * sc));
+  P.c_inv = (float)(1.0 / (fmt.full() ? top : 224.0 * sc));
+  const double kr = kKrKb[matrix][0], kb = kKrKb[matrix][1], kg = 1.0 - kr - kb;
+  P.m_rcr = (float)(2.0 * (1.0 - kr)), P.m_bcb = (float)(2.0 * (1.0 - kb));
+  P.m_gcr = (float)(-2.0 * kr * (1.0 - kr) / kg), P.m_gcb = (float)(-2.0 * kb * (1.0 - kb) / kg);
+  P.round8 = rgb_model == H2S_SRC_RGB_ROUND8;
+  hipError_t e = hipMemcpyAsync(dw, wall.data(), wall.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ds, sall.data(), sall.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && host_in) e = copy_frames(&din, in, nframes, s, fmt);
+  if (e == hipSuccess) {
+    timing_begin(c, s);  // (h2s_set_timing: the kernel alone, without the copies around it)
+    e = h2s::launch_source_rgb24(P, nframes, s);
+    timing_end(c, s);
+  }
+  for (int f = 0; host_out && f < nframes && e == hipSuccess; f++)
+    e = hipMemcpy2DAsync(rgb + (long long)f * rgb_frame_pitch, rgb_linesize, P.rgb + f * P.rfp, P.rls,
+                         3 * (size_t)out_w, out_h, hipMemcpyDeviceToHost, s);
+  // synchronous: the tables above are this call's own, and the scratch is free on return
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(c, e, "source preview");
+  return 0;
+}
+
+int h2s_preview_source_rgb24(h2s_ctx* c, const h2s_frames* in, uint8_t* rgb, int64_t rgb_linesize, int out_w,
+                             int out_h, int matrix, int rgb_model, int rgb_location, void* hip_stream) {
+  return h2s_preview_source_rgb24_batch(c, in, 1, rgb, rgb_linesize, rgb_linesize * (int64_t)out_h, out_w, out_h,
+                                        matrix, rgb_model, rgb_location, hip_stream);
 }
 
 int h2s_set_timing(h2s_ctx* c, int enabled) {

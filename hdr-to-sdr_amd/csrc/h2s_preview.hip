@@ -6,10 +6,16 @@
 // kernels are plain one-thread-per-output-sample gathers; blockIdx.z is the
 // frame of a batch (extract_frames_with_conversion_batch, src/utils.py:668-716:
 // N frames, one call); the tone-map work before them runs through k_tile.
+//
+// k_source_rgb24 is the other pane (extract_frame / extract_frames_batch,
+// src/utils.py:827-859, :629-665): the source as decoded, with no tone mapping,
+// read in place from the 10/12-bit surfaces and written as RGB24 in one launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "h2s_device.h"
+#include "h2s_srcprev.h"
 
 namespace h2s {
 
@@ -76,6 +82,83 @@ hipError_t launch_yuv8_rgb24(const uint8_t* yp, long long yls, const uint8_t* up
                              const uint8_t* glut, int nframes, hipStream_t s) {
   hipLaunchKernelGGL(k_yuv8_rgb24, dim3((w + 255) / 256, h, nframes), dim3(256), 0, s, yp, yls, up, vp, cls, yuv_fp, w,
                      h, rgb, rls, rgb_fp, glut);
+  return hipGetLastError();
+}
+
+// ---- the source pane ---------------------------------------------------------
+// One swscale context from the source format to packed RGB: nothing is rounded
+// between the resize and the matrix, and packed RGB output is horizontally 2:1
+// chroma (pixel (x, y) takes the resized chroma sample (x >> 1, y)).
+
+// separable bicubic gather of one 16-bit plane (pw x ph, samples `step` words
+// apart) at one output sample: sum of w * (code - bias), source indices clamped
+// at the edges; wx / wy point at the output sample's own Tx / Ty weights
+__device__ __forceinline__ float src_taps(const SrcPreviewParams& P, const uint8_t* __restrict__ plane, long long ls,
+                                          int step, int pw, int ph, const float* __restrict__ wx, int x0, int Tx,
+                                          const float* __restrict__ wy, int y0, int Ty, int bias) {
+  float acc = 0.0f;
+  for (int j = 0; j < Ty; j++) {
+    int r = y0 + j;
+    r = r < 0 ? 0 : (r > ph - 1 ? ph - 1 : r);
+    const uint16_t* row = (const uint16_t*)(plane + r * ls);
+    float h = 0.0f;
+    for (int i = 0; i < Tx; i++) {
+      int c = x0 + i;
+      c = c < 0 ? 0 : (c > pw - 1 ? pw - 1 : c);
+      h = fmaf(wx[i], (float)((int)((row[(long long)c * step] >> P.sh) & P.mask) - bias), h);
+    }
+    acc = fmaf(wy[j], h, acc);
+  }
+  return acc;
+}
+
+// a thread owns the horizontal pixel pair (2p, 2p + 1) of row y, which shares
+// chroma sample p; blockIdx.z is the frame.  At odd ow the last pair is half
+__global__ void __launch_bounds__(256) k_source_rgb24(const SrcPreviewParams P) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (p >= P.ow2 || y >= P.oh) return;
+  const long long f = blockIdx.z;
+  const uint8_t* yp = P.in[0] + f * P.fp[0];
+  const uint8_t* up = P.in[1] + f * P.fp[1];
+  const uint8_t* vp = P.in[2] + f * P.fp[2];
+  const int x0 = 2 * p, npx = x0 + 1 < P.ow ? 2 : 1;
+  float Y[2] = {0.0f, 0.0f};
+  if (P.identity) {
+    const uint16_t* row = (const uint16_t*)(yp + y * P.ls[0]);
+    for (int k = 0; k < npx; k++) Y[k] = (float)((int)((row[x0 + k] >> P.sh) & P.mask) - P.y_off);
+  } else {
+    for (int k = 0; k < npx; k++)
+      Y[k] = src_taps(P, yp, P.ls[0], 1, P.W, P.H, P.wx + (long long)(x0 + k) * P.Tx, P.sx[x0 + k], P.Tx,
+                      P.wy + (long long)y * P.Ty, P.sy[y], P.Ty, P.y_off);
+  }
+  const float* wcx = P.wcx + (long long)p * P.Tcx;
+  const float* wcy = P.wcy + (long long)y * P.Tcy;
+  const float Cb = P.c_inv * src_taps(P, up, P.ls[1], P.cstep, P.cw, P.ch, wcx, P.scx[p], P.Tcx, wcy, P.scy[y], P.Tcy, P.mid);
+  const float Cr = P.c_inv * src_taps(P, vp, P.ls[2], P.cstep, P.cw, P.ch, wcx, P.scx[p], P.Tcx, wcy, P.scy[y], P.Tcy, P.mid);
+  const float dr = P.m_rcr * Cr, dg = fmaf(P.m_gcr, Cr, P.m_gcb * Cb), db = P.m_bcb * Cb;
+  uint8_t o[6];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const float Yn = P.y_inv * Y[k];
+    const float c[3] = {Yn + dr, Yn + dg, Yn + db};
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const float v = c[q] < 0.0f ? 0.0f : (c[q] > 1.0f ? 1.0f : c[q]);
+      o[3 * k + q] = P.round8 ? (uint8_t)(int)floorf(fmaf(255.0f, v, 0.5f))
+                              : (uint8_t)((int)floorf(fmaf(65535.0f, v, 0.5f)) >> 8);
+    }
+  }
+  // the pair's 6 bytes lie 6 p into a row of any byte alignment: stored as a
+  // unit (unaligned vector stores), a half pair as its 3 bytes
+  uint8_t* dst = P.rgb + f * P.rfp + y * P.rls + 6LL * p;
+  if (npx == 2) memcpy(dst, o, 6);
+  else memcpy(dst, o, 3);
+}
+
+hipError_t launch_source_rgb24(const SrcPreviewParams& P, int nframes, hipStream_t s) {
+  const dim3 block(64, 4);
+  hipLaunchKernelGGL(k_source_rgb24, dim3((P.ow2 + block.x - 1) / block.x, (P.oh + block.y - 1) / block.y, nframes),
+                     block, 0, s, P);
   return hipGetLastError();
 }
 

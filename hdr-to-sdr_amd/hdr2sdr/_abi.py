@@ -35,6 +35,10 @@ RANGE_LIMITED, RANGE_FULL = 0, 1       # enum h2s_range (h2s_set_input_tags)
 CHROMA_LEFT, CHROMA_TOPLEFT = 0, 1     # enum h2s_chroma_loc
 COLOR_RANGES = {'tv': RANGE_LIMITED, 'pc': RANGE_FULL}   # ffprobe's color_range / chroma_location values
 CHROMA_LOCATIONS = {'left': CHROMA_LEFT, 'topleft': CHROMA_TOPLEFT}
+SRC_MATRIX_BT2020NC, SRC_MATRIX_BT709, SRC_MATRIX_BT601 = 0, 1, 2   # enum h2s_src_matrix (h2s_preview_source_rgb24)
+SRC_MATRICES = {'bt2020nc': SRC_MATRIX_BT2020NC, 'bt709': SRC_MATRIX_BT709, 'bt601': SRC_MATRIX_BT601}
+SRC_RGB_TRUNC16, SRC_RGB_ROUND8 = 0, 1                                # enum h2s_src_rgb
+SRC_RGB_MODELS = {'trunc16': SRC_RGB_TRUNC16, 'round8': SRC_RGB_ROUND8}
 STAGE_LINEAR, STAGE_TONEMAP, STAGE_GAMMA, STAGE_LUT, STAGE_YUV = 1, 2, 3, 4, 5
 CHROMA_BOX, CHROMA_BICUBIC = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1
@@ -65,6 +69,7 @@ EXPORTS = (
     'h2s_kernel_ms', 'h2s_set_timing', 'h2s_preview_size', 'h2s_preview_rgb24', 'h2s_preview_rgb24_batch', 'h2s_peak_reset',
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
+    'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch',
 )
 
 
@@ -199,6 +204,13 @@ def lib() -> ctypes.CDLL:
         'h2s_preview_rgb24_batch': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+        'h2s_preview_source_rgb24': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.c_void_p,
+                                                    ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+        'h2s_preview_source_rgb24_batch': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.c_int,
+                                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -25,7 +25,7 @@ SOURCES = ['h2s_kernels.hip', 'h2s_fast_lp.hip', 'h2s_fast_lp_semi.hip', 'h2s_fa
            'h2s_debug.hip', 'h2s_debug_lp_semi.hip', 'h2s_debug_lp.hip', 'h2s_fast_semi.hip', 'h2s_fast_tl.hip',
            'h2s_fast_sub422.hip', 'h2s_fast.hip', 'h2s_fast_sub444.hip', 'h2s_api.hip', 'h2s_preview.hip',
            'h2s_cube.cpp']
-HEADERS = ['h2s_device.h', 'h2s_tile.h', 'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h']
+HEADERS = ['h2s_device.h', 'h2s_tile.h', 'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_srcprev.h']
 
 
 def _hipcc() -> str:

@@ -22,6 +22,14 @@ FFMPEG_FILTER otherwise, where ``lut_enabled=False`` selects
 FFMPEG_FILTER_LEGACY_NO_LUT (src/utils.py:57-60).  ``convert_batch`` is the
 batched form (``extract_frames_with_conversion_batch`` /
 ``extract_frames_with_gpu_conversion_batch``, src/utils.py:668-716, :803-824).
+
+The GUI shows that converted frame beside the source as decoded, which the
+reference gets from ``extract_frame`` / ``extract_frames_batch``
+(src/utils.py:827-859, :629-665: ffmpeg's aspect-fit ``scale=`` and its PNG
+encoder, no tone mapping).  ``Previewer.original`` / ``original_batch`` are
+that pane, one kernel launch on the decoded surface
+(h2s_preview_source_rgb24_batch), and ``Previewer.pair`` returns both panes
+from one upload of the frame.
 """
 from __future__ import annotations
 
@@ -116,6 +124,69 @@ def parse_preview_chain(chain: str, bits_in: int = 10, transfer: str = 'smpte208
     return params, lut, box
 
 
+def source_box(vf: 'str | None') -> 'tuple[int | str, int | str]':
+    """The box of the ``-vf`` string ``extract_frame`` / ``extract_frames_batch``
+    build for the source pane (src/utils.py:851, :647):
+    ``scale=W:H:force_original_aspect_ratio=decrease`` -> (W, H); ``None`` (no
+    ``-vf``: the frame at its own size) -> ('iw', 'ih').  Anything else is not
+    the reference's aspect-fit scale and raises ValueError."""
+    if vf is None:
+        return ('iw', 'ih')
+    m = re.fullmatch(r'scale=(\w+):(\w+):force_original_aspect_ratio=decrease', vf.strip())
+    if not m:
+        raise ValueError(f'source-pane filter {vf!r} is not the reference\'s aspect-fit '
+                         '"scale=W:H:force_original_aspect_ratio=decrease"')
+    for v in m.groups():
+        if v not in ('iw', 'ih') and not (v.isdigit() and int(v) > 0):
+            raise ValueError(f'source-pane box {v!r} is not iw / ih or a positive integer')
+    return tuple(v if v in ('iw', 'ih') else int(v) for v in m.groups())   # type: ignore[return-value]
+
+
+def source_rgb(tm: Any, frames: FrameBatch, out_w: int, out_h: int, matrix: str = 'bt2020nc',
+               rgb: str = 'trunc16') -> List[np.ndarray]:
+    """Every frame of ``frames`` (host or device batch) as decoded, resized to
+    out_w x out_h and matrixed to RGB24 by one h2s_preview_source_rgb24_batch
+    call on the Tonemapper ``tm``'s context.  No tone-map state is read or
+    changed: ``tm`` needs neither params nor a LUT."""
+    if matrix not in _abi.SRC_MATRICES:
+        raise ValueError(f'matrix must be one of {sorted(_abi.SRC_MATRICES)}, got {matrix!r}')
+    if rgb not in _abi.SRC_RGB_MODELS:
+        raise ValueError(f'rgb must be one of {sorted(_abi.SRC_RGB_MODELS)}, got {rgb!r}')
+    n = frames.nframes
+    out = np.empty((n, out_h, out_w, 3), dtype=np.uint8)
+    tm._use_layouts(frames)
+    d = frames.descriptor()
+    L = _abi.lib()
+    rc = L.h2s_preview_source_rgb24_batch(tm._ctx, ctypes.byref(d), n, out.ctypes.data, 3 * out_w, 3 * out_w * out_h,
+                                          out_w, out_h, _abi.SRC_MATRICES[matrix], _abi.SRC_RGB_MODELS[rgb],
+                                          _abi.LOC_HOST, tm._stream_ptr(None))
+    if rc:
+        _abi.raise_for(rc, L.h2s_last_error(tm._ctx).decode())
+    return [out[i] for i in range(n)]
+
+
+def _per_size(frames: 'Sequence[FrameBatch]', run: Any) -> List[np.ndarray]:
+    """Frame 0 of each batch in ``frames`` through ``run`` (one batch -> its
+    images), the batches of one size, form, tags and residence as one call."""
+    out: 'list[np.ndarray | None]' = [None] * len(frames)
+    groups: 'dict[tuple, list[int]]' = {}
+    for i, f in enumerate(frames):
+        key = (f.width, f.height, f.bits, f.is_torch, getattr(f.buf, 'device', None), f.layout, f.subsampling,
+               f.color_range, f.chroma_location)
+        groups.setdefault(key, []).append(i)
+    for idx in groups.values():
+        firsts = [frames[i] if frames[i].nframes == 1 else frames[i].slice(0, 1) for i in idx]
+        if firsts[0].is_torch:
+            import torch
+            buf = torch.cat([f.buf for f in firsts])
+        else:
+            buf = np.concatenate([np.asarray(f.buf) for f in firsts])
+        batch = firsts[0]._like(buf)
+        for i, img in zip(idx, run(batch)):
+            out[i] = img
+    return out   # type: ignore[return-value]
+
+
 class Previewer:
     """One libh2s context configured for previews. The chain runs at
     bits_out 8 with eq gamma 1.0, as extract_frame_with_conversion(gamma=1.0)
@@ -173,23 +244,57 @@ class Previewer:
         CPU chain; one resize and one RGB launch per plane either way)."""
         if isinstance(frames, FrameBatch):
             return self._run(frames, width, height, gamma)
-        out: 'list[np.ndarray | None]' = [None] * len(frames)
-        groups: 'dict[tuple, list[int]]' = {}
-        for i, f in enumerate(frames):
-            key = (f.width, f.height, f.bits, f.is_torch, getattr(f.buf, 'device', None), f.layout, f.subsampling,
-                   f.color_range, f.chroma_location)
-            groups.setdefault(key, []).append(i)
-        for idx in groups.values():
-            firsts = [frames[i] if frames[i].nframes == 1 else frames[i].slice(0, 1) for i in idx]
-            if firsts[0].is_torch:
-                import torch
-                buf = torch.cat([f.buf for f in firsts])
-            else:
-                buf = np.concatenate([np.asarray(f.buf) for f in firsts])
-            batch = firsts[0]._like(buf)
-            for i, img in zip(idx, self._run(batch, width, height, gamma)):
-                out[i] = img
-        return out   # type: ignore[return-value]
+        return _per_size(frames, lambda batch: self._run(batch, width, height, gamma))
+
+    # ---- the source pane (extract_frame / extract_frames_batch) ------------------
+    def original_size(self, in_w: int, in_h: int, width: 'int | str' = PREVIEW_SIZE[0],
+                      height: 'int | str' = PREVIEW_SIZE[1]) -> Tuple[int, int]:
+        """The source pane's size for an in_w x in_h frame and the box: the
+        aspect fit of ``scale=W:H:force_original_aspect_ratio=decrease``
+        (src/utils.py:851, :647) whatever the pipeline — the original never
+        goes through libplacebo, so on that pipeline it can differ from
+        ``out_size``."""
+        return fit_size(in_w, in_h, in_w if width == 'iw' else int(width), in_h if height == 'ih' else int(height))
+
+    def _run_original(self, frames: FrameBatch, width: 'int | str', height: 'int | str', matrix: str,
+                      rgb: str) -> List[np.ndarray]:
+        ow, oh = self.original_size(frames.width, frames.height, width, height)
+        return source_rgb(self._tm, frames, ow, oh, matrix, rgb)
+
+    def original(self, frame: FrameBatch, width: 'int | str' = PREVIEW_SIZE[0], height: 'int | str' = PREVIEW_SIZE[1],
+                 matrix: str = 'bt2020nc', rgb: str = 'trunc16') -> np.ndarray:
+        """The unconverted frame 0 of ``frame`` (host or device batch) as an
+        ``(h, w, 3)`` uint8 array: what ``extract_frame`` returns, read from
+        the decoded surface on the GPU.  matrix: 'bt2020nc' (a tagged HDR
+        stream), 'bt709' or 'bt601' (swscale's default for an untagged one).
+        rgb: 'trunc16' (the 16-bit PNG a 10/12-bit source gives, opened by PIL:
+        each sample's high byte) or 'round8' (an rgb24 PNG).  No display gamma:
+        the GUI's adjust_gamma never touches the original.  The context's
+        params, LUT and peak state are neither read nor changed."""
+        return self._run_original(frame.slice(0, 1) if frame.nframes > 1 else frame, width, height, matrix, rgb)[0]
+
+    def original_batch(self, frames: 'FrameBatch | Sequence[FrameBatch]', width: 'int | str' = PREVIEW_SIZE[0],
+                       height: 'int | str' = PREVIEW_SIZE[1], matrix: str = 'bt2020nc',
+                       rgb: str = 'trunc16') -> List[np.ndarray]:
+        """``original`` for several frames (``extract_frames_batch``), in
+        ``convert_batch``'s two forms: every frame of one FrameBatch, or frame 0
+        of each batch in a list.  Frames of one size run as one libh2s call,
+        which is one kernel launch."""
+        if isinstance(frames, FrameBatch):
+            return self._run_original(frames, width, height, matrix, rgb)
+        return _per_size(frames, lambda batch: self._run_original(batch, width, height, matrix, rgb))
+
+    def pair(self, frame: FrameBatch, width: 'int | str' = PREVIEW_SIZE[0], height: 'int | str' = PREVIEW_SIZE[1],
+             gamma: float = 1.0, matrix: str = 'bt2020nc', rgb: str = 'trunc16') -> Tuple[np.ndarray, np.ndarray]:
+        """Both panes of frame 0: ``(original, converted)``, byte for byte what
+        ``original()`` and ``convert()`` return.  A host batch is moved to the
+        device once and both calls read that copy, which saves the second
+        upload."""
+        one = frame.slice(0, 1) if frame.nframes > 1 else frame
+        if not (one.is_torch and one.buf.is_cuda):
+            import torch
+            one = one.to_torch(torch.device('cuda', int(self._tm.device)))
+        return (self._run_original(one, width, height, matrix, rgb)[0], self._run(one, width, height, gamma)[0])
 
     def out_size(self, in_w: int, in_h: int, width: 'int | str' = PREVIEW_SIZE[0],
                  height: 'int | str' = PREVIEW_SIZE[1]) -> Tuple[int, int]:

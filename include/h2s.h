@@ -62,9 +62,10 @@ extern "C" {
  * Added within 3.4, with no change of either number: h2s_set_frame_layout
  * (semi-planar nv12 / p010le / p012le frame sets); h2s_set_input_subsampling
  * (4:2:2 / 4:4:4 planar input on the CPU chain); h2s_set_input_tags (a
- * source's full-range and top-left chroma tags).  No struct, signature or
- * default behaviour changes, so the symbol's presence in the loaded library
- * is the feature test. */
+ * source's full-range and top-left chroma tags); h2s_preview_source_rgb24 /
+ * _batch (the preview's source pane: the unconverted frame as RGB24).  No
+ * struct, signature or default behaviour changes, so the symbol's presence in
+ * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
 
 /* ---- error codes ------------------------------------------------------- */
@@ -533,6 +534,62 @@ int h2s_preview_rgb24_batch(h2s_ctx *ctx, const h2s_frames *in, int nframes, uin
                             int64_t rgb_linesize, int64_t rgb_frame_pitch, int out_w, int out_h,
                             double display_gamma, int rgb_location, void *hip_stream);
 
+/* ---- source pane (src/utils.py:827-859 extract_frame, :629-665
+ * extract_frames_batch; the GUI's "before" image, src/preview.py:652-653,
+ * :679-680) ------------------------------------------------------------------
+ * h2s_preview_source_rgb24_batch: nframes source frames of `in` (one size), as
+ *   decoded and with no tone mapping, as nframes RGB24 images: the restatement
+ *   of `ffmpeg -i src -vf scale=W:H:force_original_aspect_ratio=decrease ...
+ *   png`.  out_w x out_h comes from h2s_preview_size: always the aspect fit,
+ *   on the libplacebo pipeline too (the source pane never goes through
+ *   libplacebo).  rgb, rgb_linesize, rgb_frame_pitch, rgb_location and the
+ *   argument checks (geometry, resize-ratio limits, NULLs) are those of
+ *   h2s_preview_rgb24_batch.  Synchronous.
+ *   No tone-map state: the call neither reads nor changes the params, the LUT,
+ *   the options or the peak state, and works on a context that never had
+ *   h2s_set_params.  The depth is in->bits, 10 or 12 (else H2S_E_INVALID_ARG).
+ *   It reads the surfaces in place as the context's input side describes them:
+ *   h2s_set_frame_layout (planar or semi-planar, padded pitches),
+ *   h2s_set_input_subsampling (4:2:0, 4:2:2, 4:4:4 planar; 4:2:2 / 4:4:4 with a
+ *   semi-planar input is H2S_E_UNSUPPORTED) and the range tag of
+ *   h2s_set_input_tags.  The chroma-location tag is accepted and has no effect
+ *   in this model (the chroma planes are resized centre-aligned whatever the
+ *   tag says).  An unknown matrix or rgb_model is H2S_E_INVALID_ARG.
+ *   Model ([EXT], parity unpinned like the rest of the preview tail; DESIGN.md
+ *   4.4).  One swscale context, so nothing is rounded between the resize and
+ *   the matrix.  For depth b the codes y, cb, cr are the low bits (planar) or
+ *   word >> (16 - b) (semi-planar).
+ *   Resize: luma W x H -> out_w x out_h; each chroma plane from its own cw x ch
+ *     (W/2 x H/2, W/2 x H or W x H) to ow2 x out_h, ow2 = (out_w + 1) / 2:
+ *     swscale treats packed RGB output (no full_chroma_int) as horizontally
+ *     2:1 chroma, pixel (x, y) takes chroma (x >> 1, y).  Taps as in
+ *     h2s_preview_rgb24: bicubic B = 0, C = 0.6, centre-aligned, widened by the
+ *     ratio when downscaling, normalised, indices clamped at the edges;
+ *     accumulated in float.  At equal size the luma taps are the identity.
+ *   Normalisation: limited range Y' = (Y - 16 2^(b-8)) / (219 2^(b-8)), C = (C -
+ *     2^(b-1)) / (224 2^(b-8)); H2S_RANGE_FULL Y' = Y / (2^b - 1), C = (C -
+ *     2^(b-1)) / (2^b - 1).
+ *   Matrix (enum h2s_src_matrix): R' = Y' + 2 (1 - Kr) Cr, B' = Y' + 2 (1 - Kb)
+ *     Cb, G' = Y' - (2 Kr (1 - Kr) / Kg) Cr - (2 Kb (1 - Kb) / Kg) Cb, Kg = 1 -
+ *     Kr - Kb; (Kr, Kb) = BT2020NC (0.2627, 0.0593), what a tagged HDR stream
+ *     gets; BT709 (0.2126, 0.0722); BT601 (0.299, 0.114), swscale's default for
+ *     an untagged stream.  Clipped to [0, 1].
+ *   Output (enum h2s_src_rgb): TRUNC16 floor(65535 v + 0.5) >> 8 (for a 10/12-
+ *     bit source ffmpeg hands the PNG encoder rgb48be, and PIL opens a 16-bit
+ *     RGB PNG by taking each sample's high byte); ROUND8 floor(255 v + 0.5) (an
+ *     rgb24 PNG).  No display gamma: the GUI's adjust_gamma never touches the
+ *     original (src/preview.py:642).  extract_frame's single-frame form omits
+ *     -vcodec, so ffmpeg codes a JPEG there: that lossy step is not modelled.
+ * h2s_preview_source_rgb24 == the batch call with nframes = 1. */
+enum h2s_src_matrix { H2S_SRC_MATRIX_BT2020NC = 0, H2S_SRC_MATRIX_BT709 = 1, H2S_SRC_MATRIX_BT601 = 2 };
+enum h2s_src_rgb { H2S_SRC_RGB_TRUNC16 = 0, H2S_SRC_RGB_ROUND8 = 1 };
+int h2s_preview_source_rgb24(h2s_ctx *ctx, const h2s_frames *in, uint8_t *rgb, int64_t rgb_linesize,
+                             int out_w, int out_h, int matrix, int rgb_model, int rgb_location,
+                             void *hip_stream);
+int h2s_preview_source_rgb24_batch(h2s_ctx *ctx, const h2s_frames *in, int nframes, uint8_t *rgb,
+                                   int64_t rgb_linesize, int64_t rgb_frame_pitch, int out_w, int out_h,
+                                   int matrix, int rgb_model, int rgb_location, void *hip_stream);
+
 /* ---- .cube helpers (tools/generate_lut.py:28-119; lut3d's .cube parser) --
  * h2s_cube_generate: the BT.2020->BT.709 lattice, n^3 triples, .cube order,
  *   rounded exactly as the "%.6f" text the reference writes, then parsed to
@@ -550,7 +607,9 @@ int h2s_cube_parse(const char *text, int64_t len, float *rgb, int64_t cap_floats
 
 /* Kernel-duration probe for bench.py: average device time (ms) of the last
  * `count` h2s_process launches recorded with HIP events on the launch stream
- * since the last reset (count <= 0 resets the record and returns 0). */
+ * since the last reset (count <= 0 resets the record and returns 0).  A
+ * h2s_preview_source_rgb24 / _batch call records its one kernel the same way
+ * (the table and frame copies around it are outside the events). */
 double h2s_kernel_ms(h2s_ctx *ctx, int count);
 int h2s_set_timing(h2s_ctx *ctx, int enabled);
 
