@@ -397,7 +397,7 @@ __device__ __forceinline__ float hable(float in) {
 }
 
 // libplacebo spline on a PQ-domain signal: quadratic toe below the knee,
-// cubic shoulder above it (constants: spline_consts in h2s_api.hip)
+// cubic shoulder above it (constants: spline_consts in h2s_peak.h)
 // (the oracle's spline_pq_f expression: unfused where the translation unit
 // does not contract, as h2s_kernels.hip)
 template <class K>

@@ -2,6 +2,7 @@
 // instances, the dispatch over every instance, and the Y'CbCr lattice build.
 #include <hip/hip_runtime.h>
 
+#include "h2s_launch.h"
 #include "h2s_tile.h"
 
 namespace h2s {

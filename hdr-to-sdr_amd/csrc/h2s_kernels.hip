@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "h2s_device.h"
+#include "h2s_launch.h"
 #include "h2s_lpx.h"
 #include "h2s_peak.h"
 
@@ -404,8 +405,7 @@ __global__ __launch_bounds__(256) void k_chroma_bicubic(const KParams P, const C
   }
 }
 
-// ---- host-side launchers (called from h2s_api.hip) ----------------------
-enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };   // as h2s_api.hip declares it
+// ---- host-side launchers (declared in h2s_launch.h) ---------------------
 
 // k_process's instance for the launch, one runtime flag per step into the
 // template arguments (VEC, OUT8, C444, DYN, LPX)
@@ -422,7 +422,7 @@ static void launch_k(const KParams& P, dim3 grid, hipStream_t s, bool flag, Flag
 }
 
 // the generic kernel over the launch's column groups (P.gx0, P.ngx).  form
-// (enum ProcessForm, h2s_api.hip): PF_VEC the rows allow vector accesses,
+// (enum ProcessForm, h2s_launch.h): PF_VEC the rows allow vector accesses,
 // PF_OUT8 8-bit output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma
 // into P.chr444).  P.cv: dynamic peak, the frame's curve record on the device;
 // the libplacebo branch runs its exact path (h2s_lpx.h).  Dynamic-peak and
@@ -432,7 +432,7 @@ hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s) {
   if (nb == 0) return hipSuccess;
   const bool c444 = form & PF_C444, dyn = P.cv != nullptr, lpx = P.pipe == PIPE_LIBPLACEBO;
   const bool vec = (form & PF_VEC) && !c444 && !dyn, out8 = (form & PF_OUT8) != 0;
-  // 4:2:2 / 4:4:4 input: CPU chain, static peak (h2s_api.hip refuses the rest)
+  // 4:2:2 / 4:4:4 input: CPU chain, static peak (h2s_api.hip check_subsampling refuses the rest)
   if (P.sub && (dyn || lpx || P.sub > 2 || P.in_cstep != 1)) return hipErrorInvalidValue;
   if (P.sub == 1) launch_k<1>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
   else if (P.sub == 2) launch_k<2>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);

@@ -1,0 +1,47 @@
+// h2s_launch.h — the one declaration of every host-callable kernel launcher.
+// Included by the unit that defines a launcher (h2s_kernels.hip, h2s_fast.hip,
+// h2s_preview.hip) and by every host unit that calls one, so a signature or an
+// enum value that drifts apart is a compile error, not a misrouted launch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace h2s {
+
+struct KParams;           // h2s_device.h
+struct FastParams;
+struct CurveConsts;
+struct YuvLutConsts;
+struct PeakModel;         // h2s_peak.h
+struct PeakState;
+struct PeakTail;
+struct SrcPreviewParams;  // h2s_srcprev.h
+
+// launch_process's form: PF_VEC the rows allow vector accesses, PF_OUT8 8-bit
+// output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma into P.chr444)
+enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };
+
+// h2s_kernels.hip
+hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s);
+hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s);
+hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float* wy8, bool out8, hipStream_t s);
+hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& T, hipStream_t s);
+hipError_t launch_peak_curves(double2* fstat, int n, const PeakModel& M, PeakState* st, CurveConsts* out,
+                              hipStream_t s);
+hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
+
+// h2s_fast.hip
+bool fast_supported(int tonemap);
+hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub = 0);
+hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st);
+
+// h2s_preview.hip (the tap tables: resize_taps, h2s_resolve.hip; one width per axis)
+hipError_t launch_resize_u8(const uint8_t* src, int sw, int sh, long long sls, long long sfp, uint8_t* dst, int ow,
+                            int oh, long long dls, long long dfp, const float* wx, const int* sx, int Tx,
+                            const float* wy, const int* sy, int Ty, int nframes, hipStream_t s);
+hipError_t launch_yuv8_rgb24(const uint8_t* yp, long long yls, const uint8_t* up, const uint8_t* vp, long long cls,
+                             long long yuv_fp, int w, int h, uint8_t* rgb, long long rls, long long rgb_fp,
+                             const uint8_t* glut, int nframes, hipStream_t s);
+hipError_t launch_source_rgb24(const SrcPreviewParams& P, int nframes, hipStream_t s);
+
+}  // namespace h2s

@@ -55,7 +55,7 @@ struct PeakState {
 
 // The buffers of a statistics launch (k_peak_stats* then k_peak_finish, in
 // h2s_kernels.hip).  The histograms and the counter are zero on entry and are
-// left zero (h2s_api.hip clears them once, at allocation).
+// left zero (h2s_api_peak.hip frame_stats clears them once, at allocation).
 struct PeakTail {
   PeakModel M;
   double2* fstat;      // nframes: the frames' (measurement, average)

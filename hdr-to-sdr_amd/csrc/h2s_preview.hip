@@ -15,33 +15,34 @@
 #include <string.h>
 
 #include "h2s_device.h"
+#include "h2s_launch.h"
 #include "h2s_srcprev.h"
 
 namespace h2s {
 
 // separable resize of one u8 plane, taps/weights precomputed on the host per
-// output column (wx: ow x T, start sx) and row (wy: oh x T, start sy); source
+// output column (wx: ow x Tx, start sx) and row (wy: oh x Ty, start sy); source
 // indices clamp at the edges (swscale's edge handling)
 __global__ void k_resize_u8(const uint8_t* __restrict__ src, int sw, int sh, long long sls, long long sfp,
                             uint8_t* __restrict__ dst, int ow, int oh, long long dls, long long dfp,
-                            const float* __restrict__ wx, const int* __restrict__ sx,
-                            const float* __restrict__ wy, const int* __restrict__ sy, int T) {
+                            const float* __restrict__ wx, const int* __restrict__ sx, int Tx,
+                            const float* __restrict__ wy, const int* __restrict__ sy, int Ty) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= ow || y >= oh) return;
   src += blockIdx.z * sfp;
   dst += blockIdx.z * dfp;
   float acc = 0.0f;
-  for (int j = 0; j < T; j++) {
+  for (int j = 0; j < Ty; j++) {
     int r = sy[y] + j;
     r = r < 0 ? 0 : (r > sh - 1 ? sh - 1 : r);
     const uint8_t* row = src + r * sls;
     float h = 0.0f;
-    for (int i = 0; i < T; i++) {
+    for (int i = 0; i < Tx; i++) {
       int c = sx[x] + i;
       c = c < 0 ? 0 : (c > sw - 1 ? sw - 1 : c);
-      h = fmaf(wx[x * T + i], (float)row[c], h);
+      h = fmaf(wx[x * Tx + i], (float)row[c], h);
     }
-    acc = fmaf(wy[y * T + j], h, acc);
+    acc = fmaf(wy[y * Ty + j], h, acc);
   }
   const float v = floorf(acc + 0.5f);
   dst[y * dls + x] = (uint8_t)(v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v));
@@ -70,10 +71,10 @@ __global__ void k_yuv8_rgb24(const uint8_t* __restrict__ yp, long long yls, cons
 }
 
 hipError_t launch_resize_u8(const uint8_t* src, int sw, int sh, long long sls, long long sfp, uint8_t* dst, int ow,
-                            int oh, long long dls, long long dfp, const float* wx, const int* sx, const float* wy,
-                            const int* sy, int T, int nframes, hipStream_t s) {
+                            int oh, long long dls, long long dfp, const float* wx, const int* sx, int Tx,
+                            const float* wy, const int* sy, int Ty, int nframes, hipStream_t s) {
   hipLaunchKernelGGL(k_resize_u8, dim3((ow + 255) / 256, oh, nframes), dim3(256), 0, s, src, sw, sh, sls, sfp, dst, ow,
-                     oh, dls, dfp, wx, sx, wy, sy, T);
+                     oh, dls, dfp, wx, sx, Tx, wy, sy, Ty);
   return hipGetLastError();
 }
 

@@ -36,6 +36,4 @@ struct SrcPreviewParams {
   int round8;  // H2S_SRC_RGB_ROUND8: floor(255 v + 0.5); else floor(65535 v + 0.5) >> 8
 };
 
-hipError_t launch_source_rgb24(const SrcPreviewParams& P, int nframes, hipStream_t s);
-
 }  // namespace h2s

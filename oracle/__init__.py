@@ -314,7 +314,7 @@ def _nan_or(v, d):
 
 
 class PeakState:
-    """Restatement of the dynamic-peak smoothing (h2s_api.hip peak_update;
+    """Restatement of the dynamic-peak smoothing (h2s_peak.h peak_iir_step;
     PARITY UNPINNED): IIR with coefficient 1 - exp(-1 / smoothing_period) on
     the PQ peak measurement / average, bypassed by a smoothstep over the
     scene-change band (% PQ average change); the peak clamped to

@@ -11,6 +11,9 @@ four layout combinations, 4:2:2 / 4:4:4 input (the exact upsamples of the
 tile, 3 x 3 tiles, a bottom tile with 6 live rows, tile + k_process columns,
 the generic kernel, and 130x98 / 194x66 with rows padded to 16 bytes (the tile
 kernel's interior / border equalities; the hash covers the padding too).
+Tagged 4:2:0 input (h2s_set_input_tags: pc / left, tv / topleft, pc / topleft),
+planar and semi-planar, into planar output, on TAGGED_CHAINS at the same sizes
+(sub field "420-RANGE-LOCATION").
 One JSON line: {"chain/kind/WxH/sub/in->out": sha256, ...}, keys sorted.
 
   [H2S_LIB=/path/to/libh2s.so] python scripts/format_checksums.py [OUT.json]
@@ -22,7 +25,23 @@ one frame, planar and semi-planar input, at 64x32, 192x70 and 208x64; keys
 "cfg/kind/WxH/layout/stage".
 
   [H2S_LIB=...] python scripts/format_checksums.py --debug-planes OUT.npz
+
+--preview OUT.json instead hashes the RGB bytes of both preview panes (the
+engine-level calls, so that any output size can be asked for), one JSON line
+like the first mode's.  Converted pane ("chain/..."): reinhard and bt.2390
+with peak detection, a 128x64 source to 128x64 (identity), 64x32, 50x50 and
+200x40 (the last two: unequal tap widths on the two axes, either way round),
+one frame and a batch of 3, host and device RGB (device: also rows padded by
+5 bytes, the hash covers the padding), display gamma 1.0 and 2.2.  Source pane
+("source/..."): 10-bit planar 4:2:0 / 4:2:2 / 4:4:4, semi-planar 4:2:0 and
+12-bit planar 4:2:0, tv and pc, host and device input, 3 frames; the three
+matrices x both RGB models at 128x64 -> 51x25 (odd width: the half pair),
+identity and 2x up for bt2020nc / trunc16.
+
+  [H2S_LIB=...] python scripts/format_checksums.py --preview OUT.json
 """
+import ctypes
+import dataclasses
 import hashlib
 import json
 import os
@@ -46,6 +65,24 @@ CHAINS = {
 }
 FORMS = [('420', il, ol) for il in ('planar', 'semi') for ol in ('planar', 'semi')] + \
         [(sub, 'planar', ol) for sub in ('422', '444') for ol in ('planar', 'semi')]
+TAGGED_CHAINS = ('hable_lut_g22', 'lp_bt2390_peak_detect')
+TAGS = [('pc', 'left'), ('tv', 'topleft'), ('pc', 'topleft')]
+
+PREVIEW_SRC = (128, 64)
+PREVIEW_SIZES = [(128, 64), (64, 32), (50, 50), (200, 40)]
+PREVIEW_CHAINS = {'reinhard': dict(tonemapper='reinhard'), 'bt2390_peak_detect': dict(tonemapper='bt.2390')}
+
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _write(res, path):
+    line = json.dumps(res, sort_keys=True)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as fh:
+        fh.write(line + '\n')
 
 
 def debug_planes(path):
@@ -73,9 +110,83 @@ def debug_planes(path):
     return 0
 
 
+def _rgb_hash(call, tm, fb, ow, oh, extra, where, pad=0):
+    """One engine-level preview call (h2s_preview_rgb24_batch /
+    h2s_preview_source_rgb24_batch) on every frame of fb: the hash of the whole
+    RGB buffer, host or device, rows `pad` bytes longer than a row of pixels."""
+    import torch
+    from hdr2sdr import _abi
+
+    n, ls = fb.nframes, 3 * ow + pad
+    fp = ls * oh
+    if where == 'host':
+        out = np.full(n * fp, 0x55, np.uint8)
+        ptr, loc = out.ctypes.data, _abi.LOC_HOST
+    else:
+        out = torch.full((n * fp,), 0x55, dtype=torch.uint8, device='cuda')
+        ptr, loc = out.data_ptr(), _abi.LOC_DEVICE
+    tm._use_layouts(fb)
+    d = fb.descriptor()
+    L = _abi.lib()
+    rc = getattr(L, call)(tm._ctx, ctypes.byref(d), n, ptr, ls, fp, ow, oh, *extra, loc, tm._stream_ptr(None))
+    if rc:
+        _abi.raise_for(rc, L.h2s_last_error(tm._ctx).decode())
+    torch.cuda.synchronize()
+    return _sha(out if where == 'host' else out.cpu().numpy())
+
+
+def preview(path):
+    import hdr2sdr
+    import subsampling_ref as SR
+    from hdr2sdr import _abi
+    from hdr2sdr.preview import preview_params
+    from hdr2sdr.synth import synth_frames
+
+    lattice = hdr2sdr.generate_lattice(LUT_N)
+    W, H = PREVIEW_SRC
+    res = {}
+    tm = hdr2sdr.Tonemapper(0)
+    # the converted pane
+    src3 = synth_frames('smooth', NF, W, H, 10, device='cpu', seed=SEED).to_numpy()
+    for name, kw in PREVIEW_CHAINS.items():
+        tm.set_params(preview_params(**kw))
+        tm.set_lut(lattice)
+        for ow, oh in PREVIEW_SIZES:
+            for n in (1, NF):
+                fb = src3.slice(0, n).to_torch('cuda')
+                for gamma in (1.0, 2.2):
+                    for where, pad in (('host', 0), ('device', 0), ('device', 5)):
+                        if pad and (n, gamma) != (NF, 1.0):
+                            continue
+                        res[f'chain/{name}/{W}x{H}->{ow}x{oh}/n{n}/g{gamma}/{where}' + (f'+{pad}' if pad else '')] = \
+                            _rgb_hash('h2s_preview_rgb24_batch', tm, fb, ow, oh, (gamma,), where, pad)
+    # the source pane
+    forms = {}
+    fb10 = SR.round8(synth_frames('smooth', NF, W, H, 10, device='cpu', seed=SEED).to_numpy())
+    forms['10/420/planar'] = fb10
+    forms['10/420/semi'] = fb10.to_layout('semi')
+    forms.update({f'10/{s}/planar': b for s, b in SR.exact_inputs(fb10).items()})
+    forms['12/420/planar'] = synth_frames('smooth', NF, W, H, 12, device='cpu', seed=SEED).to_numpy()
+    cases = [((51, 25), m, r) for m in sorted(_abi.SRC_MATRICES) for r in sorted(_abi.SRC_RGB_MODELS)] + \
+            [((W, H), 'bt2020nc', 'trunc16'), ((2 * W, 2 * H), 'bt2020nc', 'trunc16')]
+    for form, host in sorted(forms.items()):
+        for rng in ('tv', 'pc'):
+            tagged = dataclasses.replace(host, color_range=rng)
+            for where, fb in (('host', tagged), ('device', tagged.to_torch('cuda'))):
+                for (ow, oh), matrix, model in cases:
+                    res[f'source/{form}/{rng}/{where}-in/{W}x{H}->{ow}x{oh}/{matrix}/{model}'] = \
+                        _rgb_hash('h2s_preview_source_rgb24_batch', tm, fb, ow, oh,
+                                  (_abi.SRC_MATRICES[matrix], _abi.SRC_RGB_MODELS[model]), 'host')
+    tm.close()
+    _write(res, path)
+    return 0
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == '--debug-planes':
         return debug_planes(sys.argv[2])
+    if len(sys.argv) == 3 and sys.argv[1] == '--preview':
+        return preview(sys.argv[2])
     import torch
 
     import hdr2sdr
@@ -98,15 +209,19 @@ def main():
                 host = {('420', 'planar'): fb, ('420', 'semi'): fb.to_layout('semi')}
                 if subs:
                     host.update({(s, 'planar'): b for s, b in SR.exact_inputs(fb).items()})
-                for sub, il, ol in FORMS:
+                forms = [(sub, il, ol, 'tv', 'left') for sub, il, ol in FORMS]
+                if name in TAGGED_CHAINS:
+                    forms += [('420', il, 'planar', rng, loc) for il in ('planar', 'semi') for rng, loc in TAGS]
+                for sub, il, ol, rng, loc in forms:
                     if (sub, il) not in host:
                         continue
                     h = host[(sub, il)]
                     if pad:
                         src = RowPadded(NF, W, H, params.bits_in, il, sub).load(h)
+                        src.color_range, src.chroma_location = rng, loc
                         dst = RowPadded(NF, W, H, params.bits_out, ol)
                     else:
-                        src = h.to_torch('cuda')
+                        src = dataclasses.replace(h.to_torch('cuda'), color_range=rng, chroma_location=loc)
                         dst = FrameBatch.empty_torch(NF, W, H, params.bits_out, 'cuda', ol)
                         dst.buf.fill_(0x55 if params.bits_out == 8 else 0x5555)
                     if params.peak_detect:
@@ -114,15 +229,13 @@ def main():
                     tm.process(src, dst)
                     torch.cuda.synchronize()
                     out = dst.raw() if pad else dst.to_numpy().buf
-                    res[f'{name}/{kind}/{W}x{H}/{sub}/{il}->{ol}'] = \
-                        hashlib.sha256(np.ascontiguousarray(out).tobytes()).hexdigest()
+                    tag = sub if (rng, loc) == ('tv', 'left') else f'{sub}-{rng}-{loc}'
+                    res[f'{name}/{kind}/{W}x{H}/{tag}/{il}->{ol}'] = _sha(out)
     tm.close()
-    line = json.dumps(res, sort_keys=True)
-    print(line)
     if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        with open(sys.argv[1], 'w') as fh:
-            fh.write(line + '\n')
+        _write(res, sys.argv[1])
+    else:
+        print(json.dumps(res, sort_keys=True))
     return 0
 
 

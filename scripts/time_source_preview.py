@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Latency of the preview's two panes for one 3840x2160 10-bit frame, at the
-boxes 3840x2160 and 960x540, from a host (pinned) frame and from a device frame:
+boxes 3840x2160, 1280x720 and 960x540 (--boxes picks others), from a host
+(pinned) frame and from a device frame:
 
   original()   the source pane, h2s_preview_source_rgb24_batch (one kernel)
-  convert()    the converted pane, h2s_preview_rgb24_batch (unchanged code)
+  convert()    the converted pane, h2s_preview_rgb24_batch (at 1280x720: 4K -> 720p)
   pair()       both, from one upload of the frame
   kernel       k_source_rgb24 alone (HIP events around the launch: h2s_set_timing)
 
@@ -27,7 +28,7 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, 'hdr-to-sdr_amd'))
 
-BOXES = ((3840, 2160), (960, 540))
+BOXES = ((3840, 2160), (1280, 720), (960, 540))
 
 
 def main():
@@ -38,6 +39,7 @@ def main():
     ap.add_argument('--width', type=int, default=3840)
     ap.add_argument('--height', type=int, default=2160)
     ap.add_argument('--tonemapper', default='hable')
+    ap.add_argument('--boxes', default=','.join(f'{w}x{h}' for w, h in BOXES), help='WxH,WxH,...')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.rounds * args.calls < 100 or args.warmup < 20:
@@ -58,7 +60,7 @@ def main():
     dev = host.to_torch('cuda:0')
     pv = hdr2sdr.Previewer(0, tonemapper=args.tonemapper)
     rows = []
-    for box in BOXES:
+    for box in [tuple(int(v) for v in b.split('x')) for b in args.boxes.split(',')]:
         for where, fb in (('host', host), ('device', dev)):
             o, c = pv.original(fb, *box), pv.convert(fb, *box)
             po, pc = pv.pair(fb, *box)

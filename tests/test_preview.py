@@ -116,6 +116,51 @@ def test_gpu_preview_tail_matches_oracle_tail(W, H, box, tm, lut):
         assert d.max() <= 4 and (d > 0).mean() < 2e-2
 
 
+def _engine_preview(tm, src, ow, oh):
+    """h2s_preview_rgb24 itself, at any output size (Previewer fits the aspect)."""
+    import ctypes
+    from hdr2sdr import _abi
+    out = np.empty((oh, ow, 3), np.uint8)
+    tm._use_layouts(src)
+    d = src.descriptor()
+    rc = _abi.lib().h2s_preview_rgb24(tm._ctx, ctypes.byref(d), out.ctypes.data, 3 * ow, ow, oh, 1.0,
+                                      _abi.LOC_HOST, None)
+    assert rc == 0, _abi.lib().h2s_last_error(tm._ctx).decode()
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('ow,oh', [(50, 50), (200, 40)])
+def test_gpu_preview_unequal_axis_ratios_match_oracle_tail(ow, oh):
+    """A resize whose two axes have different tap widths (128x64 -> 50x50: 12
+    column taps, 7 row taps; -> 200x40: 5 and 8), which an aspect fit never
+    asks for: the oracle tail applied to the GPU's own chain output, within
+    test_gpu_preview_tail_matches_oracle_tail's bounds (fp32 vs fp64 filter
+    weights), and a flat 8-bit field stays exactly flat, at the value the
+    unresized preview gives it."""
+    W, H = 128, 64
+    if 17 not in _LAT:
+        _LAT[17] = hdr2sdr.generate_lattice(17)
+    params = PV.preview_params('reinhard')
+    src = synth_frames('smooth', 1, W, H, 10, device='cpu', seed=3).to_numpy()
+    flat = hdr2sdr.FrameBatch.empty_numpy(1, W, H, 10)
+    flat.y[...], flat.u[...], flat.v[...] = 600, 450, 560
+    tm = hdr2sdr.Tonemapper(0, params, _LAT[17])
+    got, got_flat, same_size = _engine_preview(tm, src, ow, oh), _engine_preview(tm, flat, ow, oh), \
+        _engine_preview(tm, flat, W, H)
+    yuv8 = hdr2sdr.FrameBatch.empty_numpy(1, W, H, 8)
+    tm.process(src, yuv8)
+    tm.close()
+    want = np.zeros((oh, ow, 3), np.uint8)
+    yuv = np.ascontiguousarray(yuv8.buf[0])
+    assert oracle.lib().oracle_preview_tail(yuv.ctypes.data, W, H, ow, oh, 1.0, want.ctypes.data) == 0
+    d = np.abs(got.astype(int) - want.astype(int))
+    print(f'{W}x{H}->{ow}x{oh}: max diff {d.max()}, differing share {(d > 0).mean():.5f}')
+    assert d.max() <= 4 and (d > 0).mean() < 2e-2
+    assert np.all(same_size == same_size[0, 0])
+    assert np.all(got_flat == same_size[0, 0])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('gamma', [2.2, 0.5, 1.3])
 def test_gpu_preview_display_gamma_is_the_pil_table(gamma):
