@@ -206,7 +206,7 @@ static hipError_t table_copy(h2s_ctx* c, void* dst, const void* src, size_t byte
 }
 
 // a table of the context's: (first use) allocate, then upload
-static int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what) {
+int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what) {
   if (int rc = buf.reserve(c, bytes, what)) return rc;
   hipError_t e = table_copy(c, buf.p, src, bytes);
   return e == hipSuccess ? 0 : hip_fail(c, e, (std::string(what) + " upload").c_str());
@@ -318,6 +318,9 @@ int prepare(h2s_ctx* c, KParams* k, bool need_lut) {
   k->lut_sb = c->lut_n * c->lut_n;
   k->lut_max = (float)(c->lut_n - 1);
   k->eq_lut = c->d_eq;
+  // Dolby Vision records (h2s_set_dovi): frame 0 of the call takes record 0
+  k->dovi = c->dovi_n ? (const h2s::DoviRec*)c->d_dovi : nullptr;
+  k->dovi_n = c->dovi_n, k->dovi_f0 = 0;
   return 0;
 }
 
@@ -330,6 +333,7 @@ KParams frame_range(const KParams& k, int f0, int n) {
   }
   kf.nframes = n;
   kf.total = (long long)n * kf.ch * kf.ngx;
+  kf.dovi_f0 += f0;
   return kf;
 }
 
@@ -368,9 +372,20 @@ hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& r, cons
   F.chr444 = o.chr444;
   F.chr_w = k.W;
   F.inv_c56 = 1.0f / F.c56;
+  F.dovi = k.dovi, F.dovi_n = k.dovi_n, F.dovi_f0 = k.dovi_f0;
+  if (k.dovi) {
+    // the k_tile<2, ...> instances stage luma as the code fraction y / (2^b - 1) and read chroma
+    // back from its x8 upsampled centred codes; L'M'S' <= 1 stays inside the EOTF table, so every
+    // tile takes the branch-free body; the table's scale is the PQ one whatever params.transfer_in says
+    const double full = (double)((256 << k.x_sh) - 1);
+    F.ys = (float)(1.0 / full), F.y_off_c = 0.0f;
+    F.dv_cs = (float)(1.0 / (8.0 * full)), F.dv_cm = (float)((double)F.c_mid / full);
+    F.safe_y = F.safe_c = HUGE_VALF;
+    F.log2_lin_scale = F.log2_pq_scale;
+  }
   const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
   // (top-left 4:2:0: the SUB 3 instances, h2s_fast_tl.hip / h2s_fast_lp_tl.hip)
-  return h2s::launch_fast(F, k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s,
+  return h2s::launch_fast(F, k.dovi ? 2 : k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s,
                           k.vco ? 3 : k.sub);
 }
 
@@ -425,6 +440,9 @@ hipError_t launch_route(const h2s_ctx* c, const KParams& k, const Route& r) {
 static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
   const h2s_params& p = c->params;
   if (!c->fast_enabled || !h2s::fast_supported(k.tonemap)) return false;
+  // Dolby Vision records: the tile kernel takes the shape profile 5 carries (dovi_tile_shape,
+  // h2s_api_dovi.hip); any other record runs on the generic kernel
+  if (k.dovi && !c->dovi_tile) return false;
   if (c->lp_exact && k.pipe == h2s::PIPE_LIBPLACEBO) return false;
   // the LUT off runs on the tile kernel for the libplacebo branch only (the
   // CPU chain's legacy closed form stays on the generic kernel)
@@ -500,6 +518,7 @@ void timing_end(h2s_ctx* c, hipStream_t s) {
 static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const h2s_frames* out,
                              const h2s_frames& din, const h2s_frames& dout, const Route& r, bool dyn_peak) {
   const int nframes = k.nframes;
+  const int dovi_base = k.dovi_f0;   // (a chunk's Dolby Vision records count frames of the call)
   hipStream_t s = r.s;
   const bool host_in = in->location == H2S_LOC_HOST, host_out = out->location == H2S_LOC_HOST;
   for (Stream& ps : c->ps)
@@ -529,6 +548,7 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
     }
     if (i == 0) timing_begin(c, s_cmp);
     fill_geometry(&k, &ci, &co, nf, r.in_fmt, r.out_fmt);
+    k.dovi_f0 = dovi_base + f0;
     if (dyn_peak) {
       if (int rc = run_dynamic_peak(c, k, r.on(s_cmp))) {
         sync_all();
@@ -562,13 +582,17 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
 // h2s_process for the two layouts given (the context's own for its callers'
 // sets; a preview's chain output is planar whatever the context's is).
 // Nothing it calls reads c->in_fmt / c->out_fmt
+// dovi_f0: the call's first frame among the context's Dolby Vision records (a
+// preview that converts frame by frame passes the frame's index)
 int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
-                   Format in_fmt, Format out_fmt) {
+                   Format in_fmt, Format out_fmt, int dovi_f0) {
   if (nframes < 0) return fail(c, H2S_E_INVALID_ARG, "nframes < 0");
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
+  k.dovi_f0 = dovi_f0;
   if ((rc = check_subsampling(c, k, in_fmt))) return rc;
+  if ((rc = check_dovi(c, k, in_fmt, dovi_f0, nframes))) return rc;
   if ((rc = check_frames(c, in, c->params.bits_in, "input", in_fmt))) return rc;
   if ((rc = check_frames(c, out, c->params.bits_out, "output", out_fmt))) return rc;
   if (in->width != out->width || in->height != out->height)
@@ -791,6 +815,7 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   int rc = prepare(c, &k);
   if (rc) return rc;
   if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
+  if ((rc = check_dovi(c, k, c->in_fmt, 0, 1))) return rc;
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
@@ -906,6 +931,7 @@ int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
   int rc = prepare(c, &k);
   if (rc) return rc;
   if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
+  if ((rc = check_dovi(c, k, c->in_fmt, 0, 1))) return rc;
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_fmt))) return rc;
   // host sets are staged into tight device copies, whose alignment decides

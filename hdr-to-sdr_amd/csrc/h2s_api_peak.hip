@@ -227,6 +227,7 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   if (rc) return rc;
   if (c->in_fmt.sub != H2S_SUB_420)
     return fail(c, H2S_E_UNSUPPORTED, "h2s_peak_stats reads 4:2:0 input only (h2s_set_input_subsampling is 4:2:2 / 4:4:4)");
+  if ((rc = check_dovi(c, k, c->in_fmt, 0, nframes))) return rc;
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   if (in->location != H2S_LOC_DEVICE) return fail(c, H2S_E_INVALID_ARG, "h2s_peak_stats takes device frames");
   if (nframes == 0) return 0;

@@ -180,7 +180,8 @@ int h2s_preview_rgb24_batch(h2s_ctx* c, const h2s_frames* in, int nframes, uint8
       const h2s_frames fi = frames_at(in, f), fo = frames_at(&y8, f);
       if ((e = hipMemsetAsync(c->d_pk, 0, pb, s)) != hipSuccess)
         return restored(queued_exit(c, s, hip_fail(c, e, "peak state reset")));
-      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_fmt, PLANAR_420))) return restored(rc);
+      // (frame f of the call: its Dolby Vision record, h2s_set_dovi)
+      if ((rc = process_frames(c, &fi, &fo, 1, s, c->in_fmt, PLANAR_420, f))) return restored(rc);
     }
     if ((e = hipMemcpyAsync(c->d_pk, c->d_pk + 1, pb, hipMemcpyDeviceToDevice, s)) != hipSuccess)
       return queued_exit(c, s, hip_fail(c, e, "peak state restore"));

@@ -16,6 +16,23 @@ namespace h2s {
 
 struct CurveConsts;
 
+// A frame's Dolby Vision profile-5 record (h2s_set_dovi): the device's view of
+// include/h2s.h's h2s_dovi_curve / h2s_dovi_rpu, field for field
+// (h2s_api_dovi.hip asserts it), as the context keeps them in device memory
+struct DoviCurve {
+  int num_pivots;
+  float pivots[9];
+  int method[8];
+  float poly[8][3];
+  int mmr_order[8];
+  float mmr_const[8];
+  float mmr[8][3][7];
+};
+struct DoviRec {
+  float off[3], nl[9], lin[9];   // row-major
+  DoviCurve comp[3];
+};
+
 struct KParams {
   // geometry (luma W x H, output chroma cw x ch, ngx groups of QPT chroma columns)
   int W, H, cw, ch, ngx;
@@ -112,6 +129,13 @@ struct KParams {
   // co-sited with the even luma rows (top-left): vertical taps (0, 1) on even
   // rows, (1/2, 1/2) with row cy + 1 on odd ones; 0 whenever sub != 0
   int full, vco;
+  // Dolby Vision profile 5 (h2s_set_dovi; null: off): the context's records,
+  // read by the k_process<..., DOVI> / k_debug<..., DOVI> / k_peak_stats<2, ...>
+  // instances only (last, so that no other field moves).  Frame f of the
+  // launch takes record dovi_n == 1 ? 0 : dovi_f0 + f (dovi_f0: the launch's
+  // first frame within its call)
+  const DoviRec* dovi;
+  int dovi_n, dovi_f0;
 };
 
 constexpr int PIPE_CPU = 1, PIPE_LIBPLACEBO = 2;
@@ -266,6 +290,16 @@ struct FastParams : CurveConsts {
   // the k_tile<..., DBG = 1> instances only (launch-uniform branches there;
   // last again, so that no other field moves)
   int dbg_stage;
+  // Dolby Vision profile 5 (h2s_set_dovi), read by the k_tile<TRC = 2, ...>
+  // instances only (last again): the context's records; a tile of frame f of
+  // the launch takes record dovi_n == 1 ? 0 : dovi_f0 + f (block-uniform per
+  // tile, read through the scalar cache).  Those instances stage luma as the
+  // code fraction y / (2^b - 1) (ys, y_off_c folded so on the host) and chroma
+  // centred on c_mid; dv_cs = 1 / (8 (2^b - 1)) and dv_cm = c_mid / (2^b - 1)
+  // turn the x8 upsampled centred chroma back into its fraction
+  const DoviRec* dovi;
+  int dovi_n, dovi_f0;
+  float dv_cs, dv_cm;
 };
 
 constexpr int TBW = 64, TBH = 32;   // k_tile: luma tile of one block

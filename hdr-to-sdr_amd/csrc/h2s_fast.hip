@@ -19,6 +19,10 @@ H2S_TILE_EXTERN(1, 0, false)     // h2s_debug.hip: the debug instances
 H2S_TILE_EXTERN(1, 1, false)     // h2s_debug_lp.hip
 H2S_TILE_EXTERN(1, 0, true)      // h2s_debug_semi.hip
 H2S_TILE_EXTERN(1, 1, true)      // h2s_debug_lp_semi.hip
+H2S_TILE_DV_EXTERN(0, false)     // h2s_fast_lp_dv.hip: the Dolby Vision profile-5 instances (TRC 2)
+H2S_TILE_DV_EXTERN(0, true)      // h2s_fast_lp_dv_semi.hip
+H2S_TILE_DV_EXTERN(1, false)     // h2s_debug_lp_dv.hip
+H2S_TILE_DV_EXTERN(1, true)      // h2s_debug_lp_dv_semi.hip
 
 // YUV-premultiplied lattice (12-byte records, .cube order):
 // ((16 + 219*Y)*s + 0.5, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
@@ -48,6 +52,7 @@ bool fast_supported(int tonemap) { return tonemap >= 4 && tonemap <= 8; }
 // libplacebo curves have none).  lp: the libplacebo branch (every operator).
 // F.dbg_stage: 0 = the product kernel; 1..5 = the chain's debug instance, which
 // also writes that h2s_stage's planes (F.dbg set)
+// trc 2: a launch with Dolby Vision records (h2s_set_dovi), the k_tile<2, ...> instances
 // sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4: CPU chain product
 // instances only; anything else there is an error, never another kernel), or
 // 3 = 4:2:0 sited top-left (h2s_set_input_tags): either chain's product
@@ -63,6 +68,13 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   const size_t lds = ((size_t)F.eq_n * sizeof(uint16_t) + 15) & ~(size_t)15;
   if (tm == 7 || tm == 8 || lp) desat = 0;
   const bool dbg = F.dbg_stage != 0;
+  if (trc == 2) {   // Dolby Vision records (F.dovi): the libplacebo branch, left-sited 4:2:0; anything else is an error
+    if (!lp || sub || !F.dovi) return hipErrorInvalidValue;
+    const bool dsemi = F.in_semi || F.out_semi;
+    auto* dlaunch = dbg ? (dsemi ? launch_tile_dv<1, true> : launch_tile_dv<1, false>)
+                        : (dsemi ? launch_tile_dv<0, true> : launch_tile_dv<0, false>);
+    return dlaunch(F, tm, grid, lds, s);
+  }
   if (sub == 3) {
     if (dbg) return hipErrorInvalidValue;
     return lp ? launch_tile<0, 1, true, 3>(F, trc, tm, desat, grid, lds, s)

@@ -6,6 +6,7 @@
 //   h2s_api.hip          contexts, tables, frame staging, routing, h2s_process
 //   h2s_api_peak.hip     the dynamic peak's host side
 //   h2s_api_preview.hip  the two preview panes
+//   h2s_api_dovi.hip     Dolby Vision profile 5: the records' validation and upload
 //
 // Everything declared here has hidden visibility: the library's dynamic
 // symbols are the h2s_* calls of include/h2s.h and nothing else.
@@ -206,6 +207,12 @@ struct h2s_ctx {
   // layouts, h2s_set_input_subsampling in_fmt.sub (the output is always 4:2:0),
   // h2s_set_input_tags in_fmt.range and in_fmt.loc
   h2s::host::Format in_fmt = h2s::host::PLANAR_420, out_fmt = h2s::host::PLANAR_420;
+  // Dolby Vision profile 5 (h2s_set_dovi, h2s_api_dovi.hip): the context's copy
+  // of the caller's records; dovi_n 0: off, 1: one record for every frame,
+  // n > 1: record f for frame f of a call
+  h2s::host::Dev<h2s::DoviRec> d_dovi;
+  int dovi_n = 0;
+  bool dovi_tile = false;   // every record has the shape the tile kernel takes (dovi_tile_shape)
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
   int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
@@ -340,7 +347,12 @@ hipError_t launch_route(const h2s_ctx* c, const KParams& k, const Route& r);
 void timing_begin(h2s_ctx* c, hipStream_t s);
 void timing_end(h2s_ctx* c, hipStream_t s);
 int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
-                   Format in_fmt, Format out_fmt);
+                   Format in_fmt, Format out_fmt, int dovi_f0 = 0);
+int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what);
+
+// ---- h2s_api_dovi.hip ----
+
+int check_dovi(h2s_ctx* c, const KParams& k, Format in_fmt, int f0, int nframes);
 
 // ---- h2s_api_peak.hip ----
 

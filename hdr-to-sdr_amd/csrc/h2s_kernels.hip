@@ -55,12 +55,18 @@ __device__ __forceinline__ int ldc(const KParams& P, const uint8_t* row, int x) 
 // on the odd one, in every form (DYN and LPX included); a field (read as four
 // tap weights, no branch in the pixel loop), not a template value, so that no
 // instance is added
-template <int QPT, bool VEC, bool OUT8, bool C444 = false, bool DYN = false, bool LPX = false, int SUB = 0>
+// DOVI (h2s_set_dovi; LPX only): stage 1 is the Dolby Vision profile-5
+// front-end on the frame's record (dovi_record), in double like the rest of
+// the exact path; own instances, so that the others are what they were
+template <int QPT, bool VEC, bool OUT8, bool C444 = false, bool DYN = false, bool LPX = false, int SUB = 0,
+          bool DOVI = false>
 __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   static_assert(SUB == 0 || (!DYN && !LPX), "4:2:2 / 4:4:4 input: CPU chain, static peak");
+  static_assert(!DOVI || (LPX && SUB == 0), "Dolby Vision: the libplacebo branch, 4:2:0 input");
   LpX X;
   auto body = [&](const KParams& P, const int f, const int cy, const int cx0) {
   const int cw = P.cw, ch = P.ch;
+  const DoviRec* const rec = DOVI ? dovi_record(P, f) : nullptr;
 
   // ---- chroma: rows cy-1, cy, cy+1; columns cx0 .. cx0+QPT (halo) ----
   // (SUB 1: rows 2cy, 2cy+1 of the 4:2:2 plane, the same columns; SUB 2 below)
@@ -187,13 +193,13 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
       if (LPX) {
         // the oracle's upsample_d: horizontal (left siting) then vertical, in double
         auto hx = [&](const int (&c)[3][QPT + 1], int i) -> double {
-          const double a = lpx_chroma(P, c[i][x >> 1]);
-          return (x & 1) ? 0.5 * (a + lpx_chroma(P, c[i][(x >> 1) + 1])) : a;
+          const double a = lpx_chroma_of<DOVI>(P, c[i][x >> 1]);
+          return (x & 1) ? 0.5 * (a + lpx_chroma_of<DOVI>(P, c[i][(x >> 1) + 1])) : a;
         };
         const double wd[4] = {vw[0], vw[1], vw[2], vw[3]};   // (exact in float)
         const double cbd = j == 0 ? wd[0] * hx(ccu, 0) + wd[1] * hx(ccu, 1) : wd[2] * hx(ccu, 1) + wd[3] * hx(ccu, 2);
         const double crd = j == 0 ? wd[0] * hx(ccv, 0) + wd[1] * hx(ccv, 1) : wd[2] * hx(ccv, 1) + wd[3] * hx(ccv, 2);
-        lpx_chain<4>(P, X, lpx_luma(P, ys[j][x]), cbd, crd, px, py, r, g, b);
+        lpx_chain<4, DOVI>(P, X, lpx_luma_of<DOVI>(P, ys[j][x]), cbd, crd, px, py, r, g, b, rec);
       } else {
         chain_px<4>(P, yv, cb, cr, r, g, b, lp_qoff(P, px, py));
       }
@@ -307,7 +313,8 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
 
 // Debug/parity kernel: float RGB of frame 0 after stage STAGE, one thread per
 // pixel, generic (unvectorised) sample access.
-template <int STAGE>
+// DOVI: frame 0's Dolby Vision record (the libplacebo pipeline; own instances)
+template <int STAGE, bool DOVI = false>
 __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long npx = (long long)P.W * P.H;
@@ -338,9 +345,9 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
     auto hpd = [&](int plane, int cyy) -> double {
       const uint8_t* row = P.in[plane] + edge(P, cyy, ch) * P.in_ls[plane];
       const int k = x >> 1;
-      const double a = lpx_chroma(P, ldc(P, row, edge(P, k, cw)));
+      const double a = lpx_chroma_of<DOVI>(P, ldc(P, row, edge(P, k, cw)));
       if (!(x & 1)) return a;
-      return 0.5 * (a + lpx_chroma(P, ldc(P, row, edge(P, k + 1, cw))));
+      return 0.5 * (a + lpx_chroma_of<DOVI>(P, ldc(P, row, edge(P, k + 1, cw))));
     };
     auto upd = [&](int plane) -> double {
       const int m = y >> 1;
@@ -349,7 +356,8 @@ __global__ __launch_bounds__(256) void k_debug(const KParams P, float* out) {
       return 0.75 * hpd(plane, m) + 0.25 * hpd(plane, m + 1);
     };
     const LpX X = lpx_consts(P, P.x_peak, P.x_avg);
-    lpx_chain<STAGE < 5 ? STAGE : 4>(P, X, lpx_luma(P, ycode), upd(1), upd(2), x, y, r, g, b);
+    lpx_chain<STAGE < 5 ? STAGE : 4, DOVI>(P, X, lpx_luma_of<DOVI>(P, ycode), upd(1), upd(2), x, y, r, g, b,
+                                           DOVI ? dovi_record(P, 0) : nullptr);
   } else {
     chain_px<STAGE < 5 ? STAGE : 4>(P, yv, cb, cr, r, g, b, lp_qoff(P, x, y));
   }
@@ -410,11 +418,12 @@ __global__ __launch_bounds__(256) void k_chroma_bicubic(const KParams P, const C
 // k_process's instance for the launch, one runtime flag per step into the
 // template arguments (VEC, OUT8, C444, DYN, LPX)
 // (SUB first: the input's chroma subsampling, launch_process)
-template <int SUB, bool VEC, bool OUT8, bool C444, bool DYN, bool LPX>
+template <int SUB, bool VEC, bool OUT8, bool C444, bool DYN, bool LPX, bool DOVI>
 static void launch_k(const KParams& P, dim3 grid, hipStream_t s) {
   // no such instances: launch_process clears VEC for them, and refuses SUB with DYN / LPX
-  if constexpr (!(VEC && (C444 || DYN)) && !(SUB && (DYN || LPX)))
-    hipLaunchKernelGGL((k_process<4, VEC, OUT8, C444, DYN, LPX, SUB>), grid, dim3(256), 0, s, P);
+  // and Dolby Vision records off the libplacebo branch or with SUB
+  if constexpr (!(VEC && (C444 || DYN)) && !(SUB && (DYN || LPX)) && !(DOVI && (!LPX || SUB)))
+    hipLaunchKernelGGL((k_process<4, VEC, OUT8, C444, DYN, LPX, SUB, DOVI>), grid, dim3(256), 0, s, P);
 }
 template <int SUB, bool... B, class... Flags>
 static void launch_k(const KParams& P, dim3 grid, hipStream_t s, bool flag, Flags... rest) {
@@ -434,15 +443,29 @@ hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s) {
   const bool vec = (form & PF_VEC) && !c444 && !dyn, out8 = (form & PF_OUT8) != 0;
   // 4:2:2 / 4:4:4 input: CPU chain, static peak (h2s_api.hip check_subsampling refuses the rest)
   if (P.sub && (dyn || lpx || P.sub > 2 || P.in_cstep != 1)) return hipErrorInvalidValue;
-  if (P.sub == 1) launch_k<1>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
-  else if (P.sub == 2) launch_k<2>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
-  else launch_k<0>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx);
+  // Dolby Vision records: the libplacebo branch, 4:2:0 input (h2s_api.hip check_dovi refuses the rest)
+  const bool dovi = P.dovi != nullptr;
+  if (dovi && (!lpx || P.sub || P.vco)) return hipErrorInvalidValue;
+  if (P.sub == 1) launch_k<1>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx, false);
+  else if (P.sub == 2) launch_k<2>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx, false);
+  else launch_k<0>(P, dim3((unsigned)nb), s, vec, out8, c444, dyn, lpx, dovi);
   return hipGetLastError();
 }
 
 hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s) {
   const long long npx = (long long)P.W * P.H;
   dim3 grid((unsigned)((npx + 255) / 256)), block(256);
+  if (P.dovi) {   // frame 0's Dolby Vision record (libplacebo pipeline only: check_dovi)
+    if (P.pipe != PIPE_LIBPLACEBO || P.sub || P.vco) return hipErrorInvalidValue;
+    switch (stage) {
+      case 1: hipLaunchKernelGGL((k_debug<1, true>), grid, block, 0, s, P, out); break;
+      case 2: hipLaunchKernelGGL((k_debug<2, true>), grid, block, 0, s, P, out); break;
+      case 3: hipLaunchKernelGGL((k_debug<3, true>), grid, block, 0, s, P, out); break;
+      case 4: hipLaunchKernelGGL((k_debug<4, true>), grid, block, 0, s, P, out); break;
+      default: hipLaunchKernelGGL((k_debug<5, true>), grid, block, 0, s, P, out); break;
+    }
+    return hipGetLastError();
+  }
   switch (stage) {
     case 1: hipLaunchKernelGGL((k_debug<1>), grid, block, 0, s, P, out); break;
     case 2: hipLaunchKernelGGL((k_debug<2>), grid, block, 0, s, P, out); break;
@@ -472,9 +495,31 @@ hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float
 // taken nearest (the statistic is an estimate).  grid = (M.nblocks, frames);
 // partial[f * M.nblocks + b] = (max, sum) over block b's rows / chunks
 // one pixel's PQ-domain max(R,G,B) from its integer codes (nearest chroma)
+// TRC 2: a Dolby Vision profile-5 frame (R: its record, h2s_set_dovi): the
+// front-end's linear BT.2020 light (h2s_dovi.h, float32; 1 = 10000 nits),
+// PQ-encoded; no shortcut, since max(Lm lms) is not the largest L'M'S'
+// DoviStat: what a block's pixels share (hoisted out of the row loop by
+// k_peak_stats: block-uniform): 1 / (2^b - 1) and the record's linear matrix
+struct DoviStat {
+  float inv, lin[9];
+};
 template <int TRC>
-__device__ __forceinline__ float peak_px(const KParams& P, unsigned yc, unsigned uc, unsigned vc) {
+__device__ __forceinline__ float peak_px(const KParams& P, unsigned yc, unsigned uc, unsigned vc,
+                                         const DoviRec* R = nullptr, const DoviStat* S = nullptr) {
   yc = (yc >> P.in_sh) & P.in_mask, uc = (uc >> P.in_sh) & P.in_mask, vc = (vc >> P.in_sh) & P.in_mask;   // code_of
+  if constexpr (TRC == 2) {
+    // (model step 1's clamp to [0, 1] is no operation here: in_mask bounds every code by 2^b - 1)
+    const float sv[3] = {(float)yc * S->inv, (float)uc * S->inv, (float)vc * S->inv};
+    float v[3];
+    dovi_lms_pq<float>(*R, sv, v);
+    const float l[3] = {pq_eotf(v[0]), pq_eotf(v[1]), pq_eotf(v[2])};
+    const float r = S->lin[0] * l[0] + S->lin[1] * l[1] + S->lin[2] * l[2];
+    const float g = S->lin[3] * l[0] + S->lin[4] * l[1] + S->lin[5] * l[2];
+    const float bl = S->lin[6] * l[0] + S->lin[7] * l[1] + S->lin[8] * l[2];
+    // the linear matrix may leave every channel negative: such a pixel counts as black (PQ(0), as
+    // pq_encode's own max(y, 0) would give; stated here rather than left to it)
+    return clamp01(pq_encode(fmaxf(fmaxf(fmaxf(r, g), bl), 0.0f)));
+  }
   const float Y = (float)yc * P.y_scale + P.y_off;
   const float cb = (float)uc * P.c_scale + P.c_off, cr = (float)vc * P.c_scale + P.c_off;
   const float er = Y + P.m_rcr * cr, eg = Y + P.m_gcb * cb + P.m_gcr * cr, eb = Y + P.m_bcb * cb;
@@ -685,6 +730,12 @@ __global__ __launch_bounds__(256) void k_peak_stats(const KParams P, float2* par
     for (int i = threadIdx.x; i < PEAK_BINS; i += 256) lh[i] = 0;
   if (HIST) __syncthreads();
   const int f = blockIdx.y, b = blockIdx.x;
+  const DoviRec* const rec = TRC == 2 ? dovi_record(P, f) : nullptr;   // (block-uniform: one frame per block)
+  DoviStat ds;
+  if constexpr (TRC == 2) {
+    ds.inv = 1.0f / (float)((256 << P.x_sh) - 1);
+    for (int i = 0; i < 9; i++) ds.lin[i] = rec->lin[i];
+  }
   float mx = 0.0f, sm = 0.0f;
   HistRun run;
   for (int y = b; y < P.H; y += gridDim.x) {
@@ -694,7 +745,7 @@ __global__ __launch_bounds__(256) void k_peak_stats(const KParams P, float2* par
     float rs = 0.0f;
     for (int x = threadIdx.x; x < P.W; x += blockDim.x) {
       const int xc = (x >> 1) * P.in_cstep;   // (semi-planar: vr = ur + 1, pairs two words apart)
-      const float m = peak_px<TRC>(P, yr[x], ur[xc], vr[xc]);
+      const float m = peak_px<TRC>(P, yr[x], ur[xc], vr[xc], rec, &ds);
       mx = fmaxf(mx, m);
       rs += m;
       if (HIST) run.add(lh, m);
@@ -917,8 +968,11 @@ hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& 
   };
   const bool vec = P.W % 8 == 0 && planes_al(16, 8);
   const bool quad = P.W % 16 == 0 && P.transfer == 0 && T.form != 1 && planes_al(16, 16);
+  // (a Dolby Vision set, P.dovi: the generic row form, whatever the rows allow)
 #define H2S_PEAK_LAUNCH(HI)                                                                   \
-  if (quad && T.form == 2)                                                                    \
+  if (P.dovi)                                                                                 \
+    hipLaunchKernelGGL((k_peak_stats<2, HI>), grid, dim3(256), 0, s, P, partial, T);          \
+  else if (quad && T.form == 2)                                                               \
     hipLaunchKernelGGL((k_peak_stats_q<HI, 4>), grid, dim3(256), 0, s, P, partial, T);        \
   else if (quad)                                                                              \
     hipLaunchKernelGGL((k_peak_stats_q<HI>), grid, dim3(256), 0, s, P, partial, T);           \

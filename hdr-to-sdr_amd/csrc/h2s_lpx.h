@@ -17,6 +17,7 @@
 #include <float.h>
 
 #include "h2s_device.h"
+#include "h2s_dovi.h"
 
 namespace h2s {
 
@@ -189,15 +190,28 @@ __device__ __forceinline__ double lpx_encode(const LpX& X, double x) {
 // one pixel of the branch from its exact Y', Cb, Cr (normalised, double):
 // UPTO 1..3 = that stage's values, 4 = lut3d's 8-bit output / 255 (LUT on)
 // or the encoded BT.709 R'G'B' clipped (LUT off); px, py: the pixel (dither)
-template <int UPTO>
+// DOVI (h2s_set_dovi; R: the frame's record): yv, cb, cr are the pixel's
+// full-scale code fractions (lpx_frac) and stage 1 is the Dolby Vision
+// profile-5 front-end (h2s_dovi.h: reshape, non-linear matrix, PQ EOTF, linear
+// matrix), whatever P.transfer says
+template <int UPTO, bool DOVI = false>
 __device__ __forceinline__ void lpx_chain(const KParams& P, const LpX& X, double yv, double cb, double cr, int px,
-                                          int py, float& ro, float& go, float& bo) {
+                                          int py, float& ro, float& go, float& bo, const DoviRec* R = nullptr) {
   const double kr = 0.2627, kb = 0.0593, kg = 1.0 - kr - kb;
   const double er = yv + 2.0 * (1.0 - kr) * cr;
   const double eg = yv - 2.0 * kb * (1.0 - kb) / kg * cb - 2.0 * kr * (1.0 - kr) / kg * cr;
   const double eb = yv + 2.0 * (1.0 - kb) * cb;
   double r, g, b;
-  if (P.transfer == 1) {
+  if constexpr (DOVI) {
+    const double sv[3] = {yv, cb, cr};
+    double v[3];
+    dovi_lms_pq<double>(*R, sv, v);
+    const double s = 10000.0 / X.npl;
+    const double l[3] = {pqx_eotf(v[0]) * s, pqx_eotf(v[1]) * s, pqx_eotf(v[2]) * s};
+    r = (double)R->lin[0] * l[0] + (double)R->lin[1] * l[1] + (double)R->lin[2] * l[2];
+    g = (double)R->lin[3] * l[0] + (double)R->lin[4] * l[1] + (double)R->lin[5] * l[2];
+    b = (double)R->lin[6] * l[0] + (double)R->lin[7] * l[1] + (double)R->lin[8] * l[2];
+  } else if (P.transfer == 1) {
     r = hlgx_inv_oetf(er), g = hlgx_inv_oetf(eg), b = hlgx_inv_oetf(eb);
     const double ys = 0.2627 * r + 0.6780 * g + 0.0593 * b;
     const double w = ys > 0.0 ? 1000.0 / X.npl * pow(ys, 0.2) : 0.0;
@@ -261,6 +275,22 @@ __device__ __forceinline__ double lpx_luma(const KParams& P, int code) {
 __device__ __forceinline__ double lpx_chroma(const KParams& P, int code) {
   if (P.full) return ((double)code - (double)(128 << P.x_sh)) / (double)((256 << P.x_sh) - 1);
   return ((double)code - (double)(128 << P.x_sh)) / (double)(224 << P.x_sh);
+}
+// Dolby Vision profile 5: the full-scale code fraction c / (2^bits - 1) of a
+// luma or chroma code, whatever the range tag says (in [0, 1] for every code)
+__device__ __forceinline__ double lpx_frac(const KParams& P, int code) {
+  return (double)code / (double)((256 << P.x_sh) - 1);
+}
+// a sample's exact normalised value for lpx_chain<..., DOVI>
+template <bool DOVI>
+__device__ __forceinline__ double lpx_luma_of(const KParams& P, int code) {
+  if constexpr (DOVI) return lpx_frac(P, code);
+  else return lpx_luma(P, code);
+}
+template <bool DOVI>
+__device__ __forceinline__ double lpx_chroma_of(const KParams& P, int code) {
+  if constexpr (DOVI) return lpx_frac(P, code);
+  else return lpx_chroma(P, code);
 }
 
 }  // namespace h2s

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "h2s_device.h"
+#include "h2s_dovi.h"
 
 // Round-4 VALU trims of the step (on by default, each
 // switchable for A/B builds, scripts/build_variants.sh):
@@ -268,7 +269,11 @@ __device__ __forceinline__ bool to_linear(const FastParams& F, const float4* pq_
 // DARK: the dark re-run (px_chain): every EOTF-table read takes its first
 // segment exactly (pq_z_dark) instead of the mark staged there.  luma: the
 // desaturation's luma (DESAT instances), the CPU chain's free dark probe
-template <int TRC, int TM, int DESAT, int LP, bool DARK = false>
+// DV (the Dolby Vision instances, lin_tone TRC 2, which call this as TRC 0:
+// their light comes from the PQ table too): with a linear matrix after the
+// EOTF, PQ(max RGB) is not the largest E, so the max-RGB form of BT.2390 /
+// spline encodes sig through the PQ-encode table instead of reading emax_s
+template <int TRC, int TM, int DESAT, int LP, bool DARK = false, bool DV = false>
 __device__ __forceinline__ void tone(const FastParams& F, const CurveConsts& C, const float4* pq_lds,
                                      const float4* pqi_lds, float& r, float& g, float& b, bool safe, float emax_s,
                                      float hable_kb, float& luma_out) {
@@ -380,7 +385,9 @@ __device__ __forceinline__ void tone(const FastParams& F, const CurveConsts& C, 
     }
     const float sig = fmaxf(__builtin_fmaxf(__builtin_fmaxf(r, g), b), 1e-6f);
     float e1;
-    if (TRC == 0 && !safe) {
+    if (DV) {
+      e1 = fmaxf(pqi(pqi_lds, sig * F.npl_1e4), F.b_e1min);
+    } else if (TRC == 0 && !safe) {
       e1 = fmaxf(fmaf(emax_s, 1.0f / (float)PQ_SEG, -1.0f / (float)PQ_SEG), F.b_e1min);
     } else {  // exact PQ encode: HLG input, or the wave met the exact EOTF path
       e1 = pq_enc(sig * F.npl_1e4);
@@ -474,10 +481,103 @@ struct StepK {
 // R, G, B, with the dark re-run below.  dput: the debug planes' writer (DBG
 // = 1: the planes of F.dbg_stage, a launch-uniform test at each site; DBG = 0
 // compiles every site away)
+// The Dolby Vision profile-5 front-end of the tile kernel (TRC 2; model:
+// include/h2s.h, steps 1-3): the pixel's code fractions -> L'M'S' in the EOTF
+// table's coordinate v PQ_SEG + 1.  R is the tile's frame record (block-
+// uniform: its fields come through the scalar cache).  The shape the tile
+// kernel takes (h2s_api_dovi.hip dovi_tile_shape; any other record runs on
+// the generic kernel): luma polynomial pieces only, selected by a compare per
+// pivot; each chroma component one piece, polynomial or MMR up to order 3
+// (the record through the constant address space, so that a block-uniform
+// address gives scalar loads, as curve_of's)
+typedef __attribute__((address_space(4))) const DoviRec CDoviRec;
+typedef __attribute__((address_space(4))) const DoviCurve CDoviCurve;
+__device__ __forceinline__ void dovi_tile_front(CDoviRec& R, float s0, float s1, float s2, float& er, float& eg,
+                                                float& eb) {
+  CDoviCurve& Y = R.comp[0];
+  const int last = Y.num_pivots - 2;
+  float a0 = Y.poly[0][0], a1 = Y.poly[0][1], a2 = Y.poly[0][2];
+#pragma unroll
+  for (int i = 1; i < 8; i++) {
+    if (i <= last) {   // (block-uniform)
+      const bool hit = Y.pivots[i] <= s0;
+      a0 = hit ? Y.poly[i][0] : a0, a1 = hit ? Y.poly[i][1] : a1, a2 = hit ? Y.poly[i][2] : a2;
+    }
+  }
+  const float r0 = __builtin_amdgcn_fmed3f(fmaf(fmaf(a2, s0, a1), s0, a0), Y.pivots[0], Y.pivots[last + 1]);
+  // a chroma component's one piece (piece 0: every load has a block-uniform address)
+  const float t[7] = {s0, s1, s2, s0 * s1, s0 * s2, s1 * s2, s0 * s1 * s2};
+  auto chroma = [&](CDoviCurve& C, float x) -> float {
+    float r;
+    if (C.method[0] == 0) {   // (block-uniform)
+      r = fmaf(fmaf(C.poly[0][2], x, C.poly[0][1]), x, C.poly[0][0]);
+    } else {
+      r = C.mmr_const[0];
+      float p[7];
+#pragma unroll
+      for (int j = 0; j < 7; j++) p[j] = t[j];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        if (i < C.mmr_order[0]) {   // (block-uniform)
+#pragma unroll
+          for (int j = 0; j < 7; j++) {
+            r = fmaf(C.mmr[0][i][j], p[j], r);
+            p[j] *= t[j];
+          }
+        }
+      }
+    }
+    return __builtin_amdgcn_fmed3f(r, C.pivots[0], C.pivots[1]);
+  };
+  const float d0 = r0 - R.off[0];
+  const float d1 = chroma(R.comp[1], s1) - R.off[1];
+  const float d2 = chroma(R.comp[2], s2) - R.off[2];
+  auto row = [&](int c) {
+    const float v = clamp01(fmaf(R.nl[3 * c], d0, fmaf(R.nl[3 * c + 1], d1, R.nl[3 * c + 2] * d2)));
+    return fmaf(v, (float)PQ_SEG, 1.0f);
+  };
+  er = row(0), eg = row(1), eb = row(2);
+}
+
+// dv (TRC 2): the tile's Dolby Vision record
 template <int TRC, int TM, int DESAT, int LP, int DBG, bool NOEX, class DPut>
 __device__ __forceinline__ void lin_tone(const FastParams& F, const CurveConsts& cv, const float4* pq_lds,
                                          const float4* pqi_lds, const StepK& K, float ybs, float U, float V,
-                                         const DPut& dput, float& r, float& gg, float& bl) {
+                                         const DPut& dput, float& r, float& gg, float& bl,
+                                         const CDoviRec* dv = nullptr) {
+  if constexpr (TRC == 2) {
+    // ybs is the luma fraction (staged unscaled); chroma back from x8 centred codes
+    static_assert(TRC != 2 || LP == 1, "Dolby Vision: the libplacebo branch");
+    H2S_MARK("S1a DoVi reshape, non-linear matrix");
+    float er, eg, eb;
+    dovi_tile_front(*dv, ybs, fmaf(U, F.dv_cs, F.dv_cm), fmaf(V, F.dv_cs, F.dv_cm), er, eg, eb);
+    H2S_MARK("S1b EOTF, linear matrix");
+    // L, M, S (units of npl) from the EOTF table, then the record's linear matrix
+    auto s1 = [&](auto dark, float& o0, float& o1, float& o2) -> float {
+      float l0, l1, l2;
+      to_linear<0, PQ_SEG, true, decltype(dark)::value>(F, pq_lds, er, eg, eb, l0, l1, l2);
+      o0 = fmaf(dv->lin[0], l0, fmaf(dv->lin[1], l1, dv->lin[2] * l2));
+      o1 = fmaf(dv->lin[3], l0, fmaf(dv->lin[4], l1, dv->lin[5] * l2));
+      o2 = fmaf(dv->lin[6], l0, fmaf(dv->lin[7], l1, dv->lin[8] * l2));
+      return (l0 + l1) + l2;   // (a marked first-segment read shows here: L, M, S >= 0 do not cancel)
+    };
+    const float s1probe = s1(std::false_type{}, r, gg, bl);
+    if (DBG && F.dbg_stage == 1) {
+      float r1, g1, b1;
+      s1(std::true_type{}, r1, g1, b1);
+      dput(r1, g1, b1);
+    }
+    float luma = 0.0f;
+    tone<0, TM, DESAT, LP, false, true>(F, cv, pq_lds, pqi_lds, r, gg, bl, false, 0.0f, K.hable_kb, luma);
+    float probe = ((fabsf(r) + fabsf(gg)) + fabsf(bl)) + s1probe;
+    if constexpr (TM >= 4 && TM <= 6) probe += luma;
+    if (__builtin_amdgcn_ballot_w64(!(probe <= DARK_MARK))) {
+      H2S_MARK("rare: dark re-run");
+      s1(std::true_type{}, r, gg, bl);
+      tone<0, TM, DESAT, LP, true, true>(F, cv, pq_lds, pqi_lds, r, gg, bl, false, 0.0f, K.hable_kb, luma);
+    }
+    return;
+  }
   // E in table-segment units for the table forms: the PQ EOTF, and the HLG
   // inverse OETF on the CPU chain (the libplacebo branch keeps direct HLG)
   constexpr int ESC = TRC == 0 || !LP ? PQ_SEG : 1;
@@ -582,14 +682,15 @@ template <int TRC, int TM, int DESAT, int LP, int DBG, bool NOEX = false>
 __device__ __forceinline__ unsigned px_chain(const FastParams& F, const CurveConsts& cv, const float4* pq_lds,
                                              const float4* pqi_lds, const uint16_t* eq_lds, gu32* lut8v, const unsigned* spread_lds,
                                              __amdgpu_buffer_rsrc_t lut, const StepK K, float ybs, float U, float V,
-                                             long long di, float& oyv, float& ozv, float qoff, float ydq) {
+                                             long long di, float& oyv, float& ozv, float qoff, float ydq,
+                                             const CDoviRec* dv = nullptr) {
   constexpr bool EQM = H2S_EQMAGIC && !LP;   // see the eq lookup at the end
   const long long dpl = (long long)F.dbg_w * F.H;
   auto dput = [&](float a, float b_, float c) {
     if (di >= 0) F.dbg[di] = a, F.dbg[dpl + di] = b_, F.dbg[2 * dpl + di] = c;
   };
   float r, gg, bl;
-  lin_tone<TRC, TM, DESAT, LP, DBG, NOEX>(F, cv, pq_lds, pqi_lds, K, ybs, U, V, dput, r, gg, bl);
+  lin_tone<TRC, TM, DESAT, LP, DBG, NOEX>(F, cv, pq_lds, pqi_lds, K, ybs, U, V, dput, r, gg, bl, dv);
   H2S_MARKV("S3 encode", r, gg, bl);
   if (DBG && F.dbg_stage == 2) dput(r, gg, bl);
   f3 o;
@@ -1290,7 +1391,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   const __amdgpu_buffer_rsrc_t req = __builtin_amdgcn_make_buffer_rsrc((void*)F.eq_lut, (short)0, 2 * F.eq_n, 0x00020000);
   const unsigned eq0 = __builtin_amdgcn_raw_buffer_load_b16(req, 2 * t, 0, 0);  // out of range -> 0
   float4 pq0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const bool stage_pq = TRC == 0 || !LP || F.lp_ipt;   // block-uniform
+  const bool stage_pq = TRC != 1 || !LP || F.lp_ipt;   // block-uniform (TRC 2, Dolby Vision: the PQ EOTF of L'M'S')
   if (stage_pq && t < PQ_NSEG) {
     const __amdgpu_buffer_rsrc_t rpq = __builtin_amdgcn_make_buffer_rsrc((void*)F.pq_tab, (short)0, 16 * PQ_NSEG, 0x00020000);
     pq0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rpq, 16 * t, 0, 0));
@@ -1320,7 +1421,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     spread_lds[t] = (x | (x << 2)) & 0x249249u;
   }
   __syncthreads();   // the flags are zero before any thread's first commit sets one
-  if (LP && F.lp_ipt) {
+  // (TRC 2: the max-RGB form encodes sig through this table too, tone<..., DV>)
+  if (LP && (F.lp_ipt || TRC == 2)) {
     const __amdgpu_buffer_rsrc_t rpi = __builtin_amdgcn_make_buffer_rsrc((void*)F.pqi_tab, (short)0, 16 * PQI_NTAB, 0x00020000);
     for (int i = t; i < PQI_NTAB; i += 256)
       pqi_lds[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rpi, 16 * i, 0, 0));
@@ -1389,6 +1491,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     // frame, read through the scalar cache; the frame index is block-uniform)
     CurveConsts cv = F;
     if ((TM == 7 || TM == 8 || LP) && F.cv_frames) cv = curve_of(F.cv_frames, g.f);
+    // Dolby Vision (TRC 2): this tile's frame record (block-uniform, as the curve's)
+    const CDoviRec* const dv =
+        TRC == 2 ? (const CDoviRec*)F.dovi + __builtin_amdgcn_readfirstlane(F.dovi_n == 1 ? 0 : F.dovi_f0 + g.f) : nullptr;
     if constexpr (LP && TM == 7) {
       // the curve's constants that meet a second scalar operand in an FMA or
       // med3 (one scalar operand per VOP3 on gfx950): in VGPRs once per
@@ -1439,7 +1544,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
             const float V = SUB == 3 ? 2.0f * (h1[oh] + h1[oh + hb]) : fmaf(3.0f, h1[oh], h1[oh + hb]);
             float r, gg, bl;
             lin_tone<TRC, TM, DESAT, LP, 0, FB>(F, cv, pq_lds, pqi_lds, K, ybs, U, V, [](float, float, float) {},
-                                                 r, gg, bl);
+                                                 r, gg, bl, dv);
             H2S_MARK("S3 encode");
             vn = lp_table_read(F, K, lut8v, spread_lds, r, gg, bl, qo[s & 3]);
           }
@@ -1484,7 +1589,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       float oyv, ozv;
       // luma code (eq applied, shifted) replaces the luma sample this lane read
       reinterpret_cast<unsigned*>(yin)[yl * YST + xl + oy] = px_chain<TRC, TM, DESAT, LP, DBG, FB>(
-          F, cv, pq_lds, pqi_lds, eq_lds, lut8v, spread_lds, lut, K, ybs, U, V, di, oyv, ozv, LP ? qo[s & 3] : 0.5f, ydq);
+          F, cv, pq_lds, pqi_lds, eq_lds, lut8v, spread_lds, lut, K, ybs, U, V, di, oyv, ozv, LP ? qo[s & 3] : 0.5f, ydq, dv);
       chroma_out(s, oyv, ozv);   // (BICUBIC: this pixel's Cb, Cr into the 4:4:4 scratch)
     }
   };
@@ -1613,6 +1718,24 @@ hipError_t launch_tile(const FastParams& F, int trc, int tm, int desat, dim3 gri
 // 4:2:2 / 4:4:4 input instances <0, 0, true, SUB> (the CPU chain's product
 // kernels with the output side's layout branches) and for each chain's
 // top-left 4:2:0 instances <0, LPI, true, 3>
+// the Dolby Vision instances (TRC 2: the libplacebo branch's five operators),
+// product (DBG 0) or debug, planar or SEMI, each set in a translation unit of
+// its own (h2s_fast_lp_dv*.hip, h2s_debug_lp_dv*.hip)
+template <int DBG, bool SEMI>
+hipError_t launch_tile_dv(const FastParams& F, int tm, dim3 grid, size_t lds, hipStream_t s) {
+#define X(M)                                                                           \
+  if (tm == M) {                                                                       \
+    hipLaunchKernelGGL((k_tile<2, M, 0, 1, DBG, SEMI, 0>), grid, dim3(256), lds, s, F); \
+    return hipGetLastError();                                                          \
+  }
+  X(4) X(5) X(6) X(7) X(8)
+#undef X
+  return hipErrorInvalidValue;
+}
+#define H2S_TILE_DV_EXTERN(...) \
+  extern template hipError_t launch_tile_dv<__VA_ARGS__>(const FastParams&, int, dim3, size_t, hipStream_t);
+#define H2S_TILE_DV_INSTANCE(...) \
+  template hipError_t launch_tile_dv<__VA_ARGS__>(const FastParams&, int, dim3, size_t, hipStream_t);
 #define H2S_TILE_EXTERN(...) \
   extern template hipError_t launch_tile<__VA_ARGS__>(const FastParams&, int, int, int, dim3, size_t, hipStream_t);
 #define H2S_TILE_INSTANCE(...) \

@@ -7,6 +7,7 @@ the C-ABI library libh2s (include/h2s.h).
 from ._abi import H2SError, lib  # noqa: F401
 from .chain import (FFMPEG_CONVERT_FILTER, GPU_ONLY_TONEMAPPERS, TONEMAP,  # noqa: F401
                     TonemapParams, is_gpu_only_tonemapper, parse_filter_chain)
+from .dovi import DoviCurve, DoviRpu  # noqa: F401
 from .engine import Tonemapper  # noqa: F401
 from .frames import FrameBatch, frame_bytes  # noqa: F401
 from .lut import LUT_SIZE, cube_text, generate_cube_lines, generate_lattice, load_cube, parse_cube  # noqa: F401
@@ -18,5 +19,5 @@ __all__ = [
     'is_gpu_only_tonemapper', 'parse_filter_chain', 'Tonemapper', 'FrameBatch',
     'frame_bytes', 'LUT_SIZE', 'cube_text', 'generate_cube_lines', 'generate_lattice',
     'load_cube', 'parse_cube', 'H2SError', 'lib', 'H2SProcess', 'PipePlan', 'plan_from_argv',
-    'PREVIEW_SIZE', 'Previewer', 'fit_size', 'source_box',
+    'PREVIEW_SIZE', 'Previewer', 'fit_size', 'source_box', 'DoviCurve', 'DoviRpu',
 ]

@@ -69,7 +69,7 @@ EXPORTS = (
     'h2s_kernel_ms', 'h2s_set_timing', 'h2s_preview_size', 'h2s_preview_rgb24', 'h2s_preview_rgb24_batch', 'h2s_peak_reset',
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
-    'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch',
+    'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch', 'h2s_set_dovi',
 )
 
 
@@ -211,6 +211,8 @@ def lib() -> ctypes.CDLL:
                                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                           ctypes.c_int, ctypes.c_void_p]),
+        # (rpu: an array of dovi.H2SDoviRpu, or None)
+        'h2s_set_dovi': (ctypes.c_int, [c_ctx, ctypes.c_void_p, ctypes.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -21,12 +21,13 @@ ORACLE_LIB = os.path.join(ORACLE_DIR, 'build', 'liboracle.so')
 
 ARCH = os.environ.get('H2S_OFFLOAD_ARCH', 'gfx950')
 # (the longest compiles first, so that the parallel build does not end on one)
-SOURCES = ['h2s_kernels.hip', 'h2s_fast_lp.hip', 'h2s_fast_lp_semi.hip', 'h2s_fast_lp_tl.hip', 'h2s_debug_semi.hip',
+SOURCES = ['h2s_kernels.hip', 'h2s_debug_lp_dv_semi.hip', 'h2s_debug_lp_dv.hip', 'h2s_fast_lp_dv_semi.hip',
+           'h2s_fast_lp_dv.hip', 'h2s_fast_lp.hip', 'h2s_fast_lp_semi.hip', 'h2s_fast_lp_tl.hip', 'h2s_debug_semi.hip',
            'h2s_debug.hip', 'h2s_debug_lp_semi.hip', 'h2s_debug_lp.hip', 'h2s_fast_semi.hip', 'h2s_fast_tl.hip',
            'h2s_fast_sub422.hip', 'h2s_fast.hip', 'h2s_fast_sub444.hip', 'h2s_api.hip', 'h2s_resolve.hip',
-           'h2s_api_peak.hip', 'h2s_api_preview.hip', 'h2s_preview.hip', 'h2s_cube.cpp']
-HEADERS = ['h2s_device.h', 'h2s_tile.h', 'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_srcprev.h', 'h2s_launch.h',
-           'h2s_host.h']
+           'h2s_api_peak.hip', 'h2s_api_preview.hip', 'h2s_api_dovi.hip', 'h2s_preview.hip', 'h2s_cube.cpp']
+HEADERS = ['h2s_device.h', 'h2s_tile.h', 'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_dovi.h', 'h2s_srcprev.h',
+           'h2s_launch.h', 'h2s_host.h']
 
 
 def _hipcc() -> str:

@@ -86,7 +86,8 @@ CPU_GPU_ONLY_ERROR = ("{tonemapper} requires GPU tonemapping; this item's settin
 # "the output colors may look wrong (green/purple cast)".  The rawvideo pipe
 # the drop-in reads drops every side-data packet, so no RPU can reach libh2s:
 # the drop-in refuses such a source and the caller keeps the reference's own
-# command
+# command -- unless the caller brings the RPU's numbers
+# itself (``dovi=``, hdr2sdr/dovi.py: Tonemapper.set_dovi applies them)
 DOVI_P5_ERROR = ("Dolby Vision profile 5 needs its RPU (applied by libplacebo in the reference, "
                  "src/ffmpeg_command.py:100-106); the rawvideo pipe drops it, so libh2s cannot convert "
                  "this source — keep the reference command.")
@@ -204,7 +205,7 @@ class TonemapParams:
     def from_request(cls, request: Any, bits_in: int = 10, transfer: str = 'smpte2084',
                      properties: 'dict[str, Any] | None' = None,
                      libplacebo_available: 'bool | Callable[[], bool]' = True,
-                     cuda_interop: bool = False, **overrides: Any) -> 'TonemapParams':
+                     cuda_interop: bool = False, dovi: Any = None, **overrides: Any) -> 'TonemapParams':
         """Map a ConversionRequest-like object (src/conversion.py:26-44) to
         the params of the chain the reference's build() would emit for it.
 
@@ -213,7 +214,12 @@ class TonemapParams:
           forces the CPU chain; Dolby Vision profile 5 (which the reference
           sends to libplacebo for its RPU) raises ``ValueError`` with
           ``DOVI_P5_ERROR``: the RPU cannot cross the rawvideo pipe, so the
-          caller keeps the reference command;
+          caller keeps the reference command -- unless ``dovi`` is given (a
+          ``dovi.DoviRpu``, or a callable ``dovi(first_frame, count) ->
+          list[DoviRpu]``: the caller has the RPU's numbers from elsewhere and
+          hands them to ``Tonemapper.set_dovi`` next to the frames): then the
+          source is accepted, always on the libplacebo branch as in the
+          reference, and ``transfer`` is ignored by the kernels;
         * CPU chain (src/ffmpeg_command.py:240-247): bt.2390 / spline raise
           ``ValueError`` with the reference's message; the LUT is always on
           (``lut_enabled`` is ignored there, as ``_filter_args`` ignores it);
@@ -230,7 +236,10 @@ class TonemapParams:
         default is True."""
         plan = tonemap_plan(request, properties, libplacebo_available)
         if plan.dovi_needs_rpu:
-            raise ValueError(DOVI_P5_ERROR)
+            if dovi is None:
+                raise ValueError(DOVI_P5_ERROR)
+            # (the engine runs the libplacebo branch natively, whatever the probe says)
+            plan = replace(plan, use_libplacebo=True)
         tm = str(request.tonemapper).lower()
         bit_depth = int(getattr(request, 'bit_depth', 8))
         bits_out = 12 if bit_depth >= 12 else (10 if bit_depth == 10 else 8)

@@ -135,7 +135,13 @@ def sync_peak_state(tm: Any, shard: Any, nframes: int, device: Any = 'cpu') -> n
     """Before converting this rank's shard under dynamic peak detection: its
     frames' statistics (``tm.peak_stats``) are gathered from every rank and
     the frames before its range are fed into ``tm``'s smoothing state
-    (``tm.feed_peak``).  Returns the gathered [nframes, 2] statistics."""
+    (``tm.feed_peak``).  Returns the gathered [nframes, 2] statistics.
+    Dolby Vision records (``tm.set_dovi``) index the frames of a call, not of
+    the sequence: sharding them is out of scope, and a context that has them
+    set raises ValueError here."""
+    if getattr(tm, 'dovi_records', 0):
+        raise ValueError('frame-sharded runs do not carry Dolby Vision records (Tonemapper.set_dovi is set): '
+                         'convert a profile 5 source on one context')
     dist = _dist()
     a, _ = shard_range(nframes, dist.get_world_size(), dist.get_rank())
     fmax, favg = tm.peak_stats(shard) if shard.nframes else (np.zeros(0), np.zeros(0))

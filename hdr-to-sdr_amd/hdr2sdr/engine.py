@@ -36,6 +36,7 @@ class Tonemapper:
         self._layouts = ('planar', 'planar')   # what the context last got (h2s_set_frame_layout)
         self._subsampling = '420'              # ... (h2s_set_input_subsampling)
         self._tags = ('tv', 'left')            # ... (h2s_set_input_tags)
+        self.dovi_records = 0                  # Dolby Vision records set (set_dovi; 0: off)
         if params is not None:
             self.set_params(params)
         if lut is not None:
@@ -133,6 +134,22 @@ class Tonemapper:
             self._check(self._L.h2s_set_input_tags(self._ctx, _abi.COLOR_RANGES[color_range],
                                                    _abi.CHROMA_LOCATIONS[chroma_location]))
             self._tags = (color_range, chroma_location)
+
+    def set_dovi(self, rpus: Any = None) -> None:
+        """Dolby Vision profile 5 (h2s_set_dovi): None (or an empty sequence)
+        switches the front-end off; one ``dovi.DoviRpu`` serves every frame; a
+        sequence gives record f to frame f of each later call (a later call
+        with more frames than records raises ValueError).  The records are
+        copied; the call first waits for the context's queued launches, so
+        per-frame metadata costs one wait per batch."""
+        from .dovi import records_to_c
+        if rpus is None:
+            self._check(self._L.h2s_set_dovi(self._ctx, None, 0))
+            self.dovi_records = 0
+            return
+        arr = records_to_c(rpus)
+        self._check(self._L.h2s_set_dovi(self._ctx, ctypes.addressof(arr) if len(arr) else None, len(arr)))
+        self.dovi_records = len(arr)
 
     def _use_layouts(self, src: FrameBatch, dst: 'FrameBatch | None' = None) -> None:
         # (a call without a destination batch leaves the output side as it is)

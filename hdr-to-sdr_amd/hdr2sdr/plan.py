@@ -78,6 +78,9 @@ class PipePlan:
     # the source's tags, handed to every source batch ('tv' | 'pc', 'left' | 'topleft')
     in_range: str = 'tv'
     in_chroma_location: str = 'left'
+    # Dolby Vision profile 5: a DoviRpu for every frame, or a callable
+    # dovi(first_frame, count) -> list[DoviRpu]; None: not such a source
+    dovi: Any = None
 
     @property
     def frame_bytes_in(self) -> int:
@@ -99,7 +102,7 @@ def _remap_input(spec: str) -> str:
 def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[str, Any] | None' = None,
                    mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar',
                    in_subsampling: str = '420', in_range: str = 'tv',
-                   in_chroma_location: str = 'left') -> PipePlan:
+                   in_chroma_location: str = 'left', dovi: Any = None) -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
 
     in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
@@ -141,13 +144,26 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     hdr: ``_probe_hdr_metadata`` output (src/utils.py:329-372). Inside
     ffmpeg, vf_tonemap reads MaxCLL from frame side data. Raw pipes drop side
     data, so it is passed to libh2s explicitly here.
+    dovi: for a Dolby Vision profile 5 source, the RPU's numbers from
+    elsewhere (ffprobe frame side data, an RPU tool): one ``dovi.DoviRpu`` for
+    every frame, or a callable ``dovi(first_frame, count) -> list[DoviRpu]``
+    that the run loop asks per batch (``Tonemapper.set_dovi``).  The
+    reference's argv for such a source is always a libplacebo chain
+    (src/ffmpeg_command.py:96-144); any other chain raises ValueError.  The
+    unspecified ``color_transfer`` such streams carry is not an error: the
+    kernels ignore the transfer once records are set.
+
     Raises ValueError for an argv without a tone-map filter graph, and for a
-    Dolby Vision profile 5 source (its RPU cannot cross the pipe)."""
+    Dolby Vision profile 5 source without ``dovi`` (its RPU cannot cross the
+    pipe)."""
     argv = list(argv)
-    if is_dovi_profile5(properties):
+    p5 = is_dovi_profile5(properties)
+    if p5 and dovi is None:
         # src/ffmpeg_command.py:100-106: profile 5 needs the RPU libplacebo
         # applies; the rawvideo decode pipe drops it
         raise ValueError(DOVI_P5_ERROR)
+    if dovi is not None and not p5:
+        raise ValueError('dovi= is for a Dolby Vision profile 5 source (properties: is_dolby_vision, dovi_profile 5)')
     if '-i' not in argv or '-filter_complex' not in argv:
         raise ValueError('argv has no -i / -filter_complex: not a build() conversion command')
     exe = argv[0]
@@ -184,6 +200,8 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     if bits_in not in (10, 12):
         raise ValueError(f'{bits_in}-bit sources are not HDR10/HLG inputs')
     trc = properties.get('color_transfer', '') or ''
+    if p5 and trc not in TRANSFERS:
+        trc = ''      # profile 5 streams are tagged unspecified / unknown; the records define the decode
     if trc not in TRANSFERS:
         raise ValueError(f'unsupported source transfer {trc!r} (expected smpte2084 or arib-std-b67)')
     extra: 'dict[str, Any]' = {}
@@ -194,6 +212,9 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
             extra['mastering_max'] = float(hdr['mastering_max'])
     params, lut_path = parse_filter_chain(chain, bits_in=bits_in, bits_out=bits_out,
                                           transfer=TRANSFERS[trc], mode=mode, **extra)
+    if p5 and params.resolved_pipeline() != 'libplacebo':
+        raise ValueError('a Dolby Vision profile 5 source converts on the libplacebo branch only; '
+                         'this argv carries the CPU chain (the reference shows wrong colours there)')
     W, H = int(properties['width']), int(properties['height'])
     fps = out[out.index('-r') + 1] if '-r' in out else str(properties.get('frame_rate', 24.0))
     # output path = last positional before the optional trailing -y
@@ -240,7 +261,7 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     return PipePlan(decode=decode, encode=encode, params=params, lut_path=lut_path, width=W, height=H,
                     input_path=input_path, output_path=output_path, reference_argv=argv,
                     in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling,
-                    in_range=in_range, in_chroma_location=in_chroma_location)
+                    in_range=in_range, in_chroma_location=in_chroma_location, dovi=dovi)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -330,6 +351,9 @@ class H2SProcess:
                 if item is None:
                     break
                 slot, n = item
+                if self.plan.dovi is not None:   # this batch's records (frames self.frames .. + n)
+                    from .dovi import resolve_records
+                    self._tm.set_dovi(resolve_records(self.plan.dovi, self.frames, n))
                 self._tm.process(self._src[slot], self._dst, nframes=n)   # synchronous for host frames
                 self._free.put(slot)
                 self.enc.stdin.write(dst_mv[:n * fout])

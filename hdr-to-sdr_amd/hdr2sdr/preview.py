@@ -201,8 +201,10 @@ class Previewer:
 
     def __init__(self, device: int = 0, tonemapper: str = 'reinhard', lut_enabled: bool = True,
                  bits_in: int = 10, transfer: str = 'smpte2084', lattice: Optional[np.ndarray] = None,
-                 use_gpu: bool = False, params: Optional[TonemapParams] = None, **kw: Any):
+                 use_gpu: bool = False, params: Optional[TonemapParams] = None, dovi: Any = None, **kw: Any):
         from .engine import Tonemapper
+        if dovi is not None and params is None:
+            use_gpu = True     # a Dolby Vision profile 5 source previews through libplacebo, GPU toggle or not
         if params is None:
             params = preview_params(tonemapper, lut_enabled, use_gpu, bits_in, transfer, **kw)
         elif params.bits_out != 8 or params.gamma != 1.0:
@@ -212,6 +214,16 @@ class Previewer:
         self._tm = Tonemapper(device, self.params)
         if lut_enabled:
             self._tm.set_lut(lattice if lattice is not None else _lut.generate_lattice(_lut.LUT_SIZE))
+        if dovi is not None:
+            self.set_dovi(dovi)
+
+    def set_dovi(self, rpus: Any = None) -> None:
+        """The Dolby Vision profile 5 records of the converted pane
+        (``Tonemapper.set_dovi``): one ``DoviRpu`` for every frame, or a
+        sequence with record f for frame f of a ``convert_batch`` FrameBatch
+        (``convert`` shows frame 0 with record 0).  The source pane ignores
+        them, as the reference's ``extract_frame`` shows the raw codes."""
+        self._tm.set_dovi(rpus)
 
     @classmethod
     def from_chain(cls, chain: str, device: int = 0, bits_in: int = 10, transfer: str = 'smpte2084',

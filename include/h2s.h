@@ -63,7 +63,8 @@ extern "C" {
  * (semi-planar nv12 / p010le / p012le frame sets); h2s_set_input_subsampling
  * (4:2:2 / 4:4:4 planar input on the CPU chain); h2s_set_input_tags (a
  * source's full-range and top-left chroma tags); h2s_preview_source_rgb24 /
- * _batch (the preview's source pane: the unconverted frame as RGB24).  No
+ * _batch (the preview's source pane: the unconverted frame as RGB24);
+ * h2s_set_dovi (Dolby Vision profile 5: per-frame RPU records).  No existing
  * struct, signature or default behaviour changes, so the symbol's presence in
  * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -482,6 +483,94 @@ int h2s_set_input_subsampling(h2s_ctx *ctx, int subsampling);
  * Only the arguments of later launches change, so the call does not wait for
  * queued work.  An unknown value or a NULL ctx is H2S_E_INVALID_ARG. */
 int h2s_set_input_tags(h2s_ctx *ctx, int range, int chroma_location);
+
+/* ---- Dolby Vision profile 5 (default: off) ---------------------------------
+ * A profile-5 stream has no HDR10-compatible base layer: its codes are
+ * IPT-PQ-c2 and mean something only after the frame's RPU has reshaped them.
+ * The reference sends such a source to libplacebo even with GPU acceleration
+ * off (src/ffmpeg_command.py:96-144); its CPU chain shows green and purple.
+ * The RPU does not cross a rawvideo pipe, so the caller hands its numbers (a
+ * few hundred per frame: ffprobe frame side data, an RPU tool) to the context
+ * next to the frames.  Parsing the RPU bitstream is not part of this library.
+ *
+ * Model ([EXT], PARITY UNPINNED like the rest of the libplacebo branch:
+ * libplacebo is absent).  It restates pl_shader_dovi_reshape
+ * followed by libplacebo's Dolby Vision decode, written from memory of
+ * libplacebo's source, not compared against it.  For input depth b (10 or 12)
+ * and the frame's record R, per luma pixel:
+ *   1. Signal: (y, cb, cr) = the luma code and the two chroma codes upsampled
+ *      to luma resolution by the branch's S1 upsampler (left-sited bilinear,
+ *      params.chroma_edge; the lp_p010 mask applies to the codes first);
+ *      s = clamp((y, cb, cr) / (2^b - 1), 0, 1).  The range tag has no effect:
+ *      an RPU is defined on the full-scale code fraction.
+ *   2. Reshape: component c reads the unreshaped s of all three.  It has
+ *      num_pivots in [2, 9] ascending pivots; piece k is the largest k <=
+ *      num_pivots - 2 with pivots[k] <= s_c (k = 0 below the first pivot).
+ *      method[k] 0, polynomial: r = a0 + a1 s_c + a2 s_c^2 (poly[k]).
+ *      method[k] 1, MMR of order o = mmr_order[k] in {1, 2, 3}: with the terms
+ *      t = (s0, s1, s2, s0 s1, s0 s2, s1 s2, s0 s1 s2),
+ *      r = mmr_const[k] + sum_{i=1..o} sum_{j=0..6} mmr[k][i-1][j] t_j^i.
+ *      r_c = clamp(r, pivots[0], pivots[num_pivots - 1]).
+ *   3. Non-linear matrix: v = clamp(nonlinear (r - nonlinear_offset), 0, 1):
+ *      L'M'S'.  The clamp to 1 is this model's own, not libplacebo's: beyond
+ *      it lies more than 10000 nits.
+ *   4. EOTF: lms = PQ_EOTF(v), 1 = 10000 nits.
+ *   5. Linear matrix: rgb = linear lms: linear BT.2020 light, scaled to units
+ *      of npl as S1 does; not clamped (S2 treats a negative channel as it does
+ *      for any source).  `linear` is the complete L, M, S -> BT.2020 R, G, B
+ *      matrix.
+ * From here on the libplacebo branch runs unchanged: every operator, both
+ * lp_tone forms, the LUT on or off, peak_detect, every output depth and
+ * layout.  The trim metadata (L1 / L2 / L5 / L6) is not modelled: with
+ * peak_detect the detected peak governs, as in the reference.
+ *
+ * h2s_set_dovi(ctx, rpu, n): n == 0 (rpu NULL or not) switches the front-end
+ * off, the default: nothing else changes then, the same kernels run with
+ * byte-identical output.  n == 1: one record for every frame.  n > 1: record
+ * f for frame f of each later call; a later call with nframes > n is
+ * H2S_E_INVALID_ARG.  The records are copied into context-owned device
+ * memory; like h2s_set_params the call first waits for the context's queued
+ * launches, so dynamic metadata costs one wait per batch (a stream-ordered
+ * upload is out of scope).  Each of these is H2S_E_INVALID_ARG with a message:
+ * a pivot count outside [2, 9]; pivots not ascending or outside [0, 1]; a
+ * method or an order outside its enum; a coefficient that is not finite.
+ *
+ * With a record set: params.transfer_in is ignored; the pipeline must resolve
+ * to LIBPLACEBO (H2S_PIPE_CPU_CHAIN, or AUTO with a CPU-chain operator, is
+ * H2S_E_UNSUPPORTED: the reference has no such path and shows wrong colours
+ * there); H2S_CHROMA_TOPLEFT is H2S_E_UNSUPPORTED; 4:2:2 / 4:4:4 input stays
+ * the branch's own refusal; input may be planar or semi-planar, in device or
+ * host memory (in the host chunk pipeline record indices count frames of the
+ * call, not of the chunk).  The records are honoured by h2s_process and
+ * h2s_query_path, h2s_debug_float (frame 0: record 0), h2s_peak_stats and the
+ * statistics h2s_process queues under peak_detect (per-pixel PQ(max R, G, B)
+ * of the decoded light, nearest chroma), and h2s_preview_rgb24 / _batch.
+ * h2s_preview_source_rgb24 ignores them: the reference's extract_frame shows
+ * the raw codes too, because swscale applies no RPU.
+ * Routes: the tile kernel has instances for the shape profile 5 actually
+ * carries -- luma polynomial pieces only (up to 8), each chroma component a
+ * single piece, polynomial or MMR up to order 3 -- for the libplacebo
+ * branch's five operators, planar and semi-planar (float32, like the rest of
+ * that kernel; H2S_PATH_TILE / _TILE_TAIL).  A set in which any record has
+ * another shape (a luma MMR, multi-piece chroma) runs on the generic kernel
+ * (H2S_PATH_GENERIC; never a third route), as do tails, widths under 64,
+ * H2S_OPT_FAST_PATH = 0 and H2S_OPT_LP_EXACT: there the front-end is in double
+ * precision like the rest of its stages 1-3.  h2s_debug_float reports the
+ * tile kernel's own arithmetic on the tile path. */
+typedef struct h2s_dovi_curve {
+  int32_t num_pivots;      /* 2..9 */
+  float   pivots[9];
+  int32_t method[8];       /* 0 polynomial, 1 MMR */
+  float   poly[8][3];
+  int32_t mmr_order[8];    /* 1..3 */
+  float   mmr_const[8];
+  float   mmr[8][3][7];
+} h2s_dovi_curve;
+typedef struct h2s_dovi_rpu {
+  float nonlinear_offset[3], nonlinear[9], linear[9];   /* row-major */
+  h2s_dovi_curve comp[3];
+} h2s_dovi_rpu;
+int h2s_set_dovi(h2s_ctx *ctx, const h2s_dovi_rpu *rpu, int n);
 
 /* ---- dynamic peak (params.peak_detect, BT.2390 / spline) -----------------
  * h2s_peak_reset: forget the smoothing state (a new sequence / scene cut).
