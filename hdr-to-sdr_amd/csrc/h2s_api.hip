@@ -881,9 +881,8 @@ int h2s_set_option(h2s_ctx* c, int key, int64_t value) {
     case H2S_OPT_TEST_FAIL_AFTER_LAUNCH:
       c->fail_after_launch = value != 0;
       return 0;
-    case H2S_OPT_TEST_PEAK_FORM:
-      c->peak_form = (int)value;
-      return 0;
+    case H2S_OPT_PRIVATE_BASE + 2:   // reserved: H2S_OPT_TEST_PEAK_FORM's key (the quad form's A/B, decided in round 6)
+      return fail(c, H2S_E_INVALID_ARG, "option 0x7f000002 is reserved (the peak statistics form is no option)");
     case H2S_OPT_TEST_PEAK_BLOCKS:
       if (value < 1 || value > h2s::PEAK_BLOCKS_MAX) return fail(c, H2S_E_INVALID_ARG, "peak blocks must be in [1, 256]");
       c->peak_blocks = (int)value;

@@ -67,7 +67,6 @@ static int frame_stats(h2s_ctx* c, const KParams& k, hipStream_t s, h2s::PeakSta
   T.st = st;
   T.out = out;
   T.nframes = nframes;
-  T.form = c->peak_form;
   hipError_t e = h2s::launch_peak_stats(k, d_part, T, s);
   return e == hipSuccess ? 0 : hip_fail(c, e, "peak statistics");
 }

@@ -150,6 +150,38 @@ __host__ __device__ __forceinline__ int chroma_edge_at(int i, int n, int mode) {
   return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
 }
 
+// XCD-aware block remap: hardware deals blocks round-robin over 8 XCDs;
+// give XCD x the contiguous logical range [x*per(+rem), ...).  Bijective.
+__device__ __forceinline__ long long xcd_remap(long long b, long long nb) {
+  const long long xcd = b & 7, idx = b >> 3, per = nb >> 3, rem = nb & 7;
+  return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
+}
+
+// the 16-bit words of a 16-byte / 8-byte load, in memory order, and the
+// store word(s) of N codes, 8 or 16 bits each (N = 8: uint2 / uint4, N = 4:
+// unsigned / uint2).  Pure bit moves: code_of / expand_code are the caller's
+__device__ __forceinline__ void unpack16(const uint4 q, unsigned (&w)[8]) {
+  w[0] = q.x & 0xffff, w[1] = q.x >> 16, w[2] = q.y & 0xffff, w[3] = q.y >> 16;
+  w[4] = q.z & 0xffff, w[5] = q.z >> 16, w[6] = q.w & 0xffff, w[7] = q.w >> 16;
+}
+__device__ __forceinline__ void unpack16(const uint2 q, unsigned (&w)[4]) {
+  w[0] = q.x & 0xffff, w[1] = q.x >> 16, w[2] = q.y & 0xffff, w[3] = q.y >> 16;
+}
+template <bool OUT8, int N>
+__device__ __forceinline__ auto pack_codes(const int (&c)[N]) {
+  constexpr int PER = OUT8 ? 4 : 2, SH = OUT8 ? 8 : 16, NW = N / PER;
+  unsigned w[NW];
+#pragma unroll
+  for (int i = 0; i < NW; i++) {
+    w[i] = (unsigned)c[PER * i];
+#pragma unroll
+    for (int k = 1; k < PER; k++) w[i] |= (unsigned)c[PER * i + k] << (SH * k);
+  }
+  if constexpr (NW == 4) return make_uint4(w[0], w[1], w[2], w[3]);
+  else if constexpr (NW == 2) return make_uint2(w[0], w[1]);
+  else return w[0];
+}
+
 // Constants of the PQ-domain curves (BT.2390 / spline) in the fast kernel's
 // folded form.  They are the only parameters that change from frame to frame
 // under dynamic peak detection, so a launch can take one record per frame.

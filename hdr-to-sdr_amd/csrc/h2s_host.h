@@ -214,7 +214,6 @@ struct h2s_ctx {
   int dovi_n = 0;
   bool dovi_tile = false;   // every record has the shape the tile kernel takes (dovi_tile_shape)
   int peak_blocks = h2s::PEAK_BLOCKS;   // H2S_OPT_TEST_PEAK_BLOCKS (private A/B hook)
-  int peak_form = 0;      // H2S_OPT_TEST_PEAK_FORM (private A/B hook)
   bool serial_host = false;  // H2S_HOST_SERIAL=1: one H2D, kernel, D2H per call (no chunk pipeline)
   int tiles_per_block = 8;  // k_tile: tiles one block walks (H2S_TILES_PER_BLOCK overrides, 1..64)
   h2s::host::Dev<uint16_t> d_eq;

@@ -1,4 +1,6 @@
-// h2s_kernels.hip — gfx950 kernels for the HDR->SDR hot path.
+// h2s_kernels.hip — the chain's exact restatement for gfx950: k_process,
+// k_debug, k_chroma_bicubic, k_build_lut8x and their launchers, built without
+// FMA contraction so that the float arithmetic rounds where the oracle's does.
 //
 // k_process: the whole per-frame chain of src/utils.py:38-42 fused into one
 // pass over HBM: read packed 10/12-bit planar 4:2:0, upsample chroma, S1..S4
@@ -7,27 +9,18 @@
 // sample each) of one chroma row of one frame; the flattened item index runs
 // columns fastest, so a wavefront reads contiguous row segments (16-B Y loads,
 // 8-B chroma loads per lane).  Blocks are remapped so that each XCD walks a
-// contiguous range of rows (chroma halo rows and LUT lines stay in its L2).
+// contiguous range of rows (chroma halo rows and LUT lines stay in its L2;
+// xcd_remap, h2s_device.h).
 #include <hip/hip_runtime.h>
-
-#include <vector>
 
 #include "h2s_device.h"
 #include "h2s_launch.h"
 #include "h2s_lpx.h"
-#include "h2s_peak.h"
 
 namespace h2s {
 
 // the upsampler's edge rule (params.chroma_edge; oracle/h2s_oracle.c edge())
 __device__ __forceinline__ int edge(const KParams& P, int i, int n) { return chroma_edge_at(i, n, P.chroma_edge); }
-
-// XCD-aware block remap: hardware deals blocks round-robin over 8 XCDs;
-// give XCD x the contiguous logical range [x*per(+rem), ...).  Bijective.
-__device__ __forceinline__ long long xcd_remap(long long b, long long nb) {
-  const long long xcd = b & 7, idx = b >> 3, per = nb >> 3, rem = nb & 7;
-  return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
 
 __device__ __forceinline__ int ld16(const uint8_t* row, int x) {
   return *reinterpret_cast<const uint16_t*>(row + 2 * x);
@@ -82,16 +75,17 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
     if (VEC && full && QPT == 4) {
       const int hx = edge(P, cx0 + 4, cw);
       if (P.in_cstep == 2) {   // semi-planar: four (Cb, Cr) pairs in one 16-byte load
+        // (the three 16-byte unpacks of this kernel are spelt out: through unpack16 the exact-path
+        // instances compile to other code, profiles/peak_unit/build.md)
         const uint4 q = *reinterpret_cast<const uint4*>(ru + 4 * cx0);
         const unsigned w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int k = 0; k < 4; k++) ccu[i][k] = code_of(P, w[k] & 0xffff), ccv[i][k] = code_of(P, w[k] >> 16);
       } else {
-        const uint2 a = *reinterpret_cast<const uint2*>(ru + 2 * cx0);
-        const uint2 b = *reinterpret_cast<const uint2*>(rv + 2 * cx0);
         // (code_of: h2s_lp_p010 TRUNCATE drops the two low bits)
-        const unsigned su[4] = {a.x & 0xffff, a.x >> 16, a.y & 0xffff, a.y >> 16};
-        const unsigned sv[4] = {b.x & 0xffff, b.x >> 16, b.y & 0xffff, b.y >> 16};
+        unsigned su[4], sv[4];
+        unpack16(*reinterpret_cast<const uint2*>(ru + 2 * cx0), su);
+        unpack16(*reinterpret_cast<const uint2*>(rv + 2 * cx0), sv);
 #pragma unroll
         for (int k = 0; k < 4; k++) ccu[i][k] = code_of(P, su[k]), ccv[i][k] = code_of(P, sv[k]);
       }
@@ -131,6 +125,7 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
       const uint8_t* rv = P.in[2] + f * P.in_fp[2] + (2 * cy + j) * P.in_ls[2];
       int cu4[2 * QPT], cv4[2 * QPT];
       if (VEC && full && QPT == 4) {
+        // (spelt out, not unpack16: see the semi-planar chroma load above)
         const uint4 a = *reinterpret_cast<const uint4*>(ru + 2 * x0), b = *reinterpret_cast<const uint4*>(rv + 2 * x0);
         const unsigned wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
@@ -157,6 +152,7 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   for (int j = 0; j < 2; j++) {
     const uint8_t* ry = P.in[0] + f * P.in_fp[0] + (2 * cy + j) * P.in_ls[0];
     if (VEC && full && QPT == 4) {
+      // (spelt out, not unpack16: see the semi-planar chroma load above)
       const uint4 a = *reinterpret_cast<const uint4*>(ry + 2 * x0);
       const unsigned w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
@@ -225,19 +221,8 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   for (int j = 0; j < 2; j++) {
     uint8_t* ry = P.out[0] + f * P.out_fp[0] + (2 * cy + j) * P.out_ls[0];
     if (VEC && full && QPT == 4) {
-      if (OUT8) {
-        uint2 w;
-        w.x = (unsigned)yo[j][0] | ((unsigned)yo[j][1] << 8) | ((unsigned)yo[j][2] << 16) | ((unsigned)yo[j][3] << 24);
-        w.y = (unsigned)yo[j][4] | ((unsigned)yo[j][5] << 8) | ((unsigned)yo[j][6] << 16) | ((unsigned)yo[j][7] << 24);
-        *reinterpret_cast<uint2*>(ry + x0) = w;
-      } else {
-        uint4 w;
-        w.x = (unsigned)yo[j][0] | ((unsigned)yo[j][1] << 16);
-        w.y = (unsigned)yo[j][2] | ((unsigned)yo[j][3] << 16);
-        w.z = (unsigned)yo[j][4] | ((unsigned)yo[j][5] << 16);
-        w.w = (unsigned)yo[j][6] | ((unsigned)yo[j][7] << 16);
-        *reinterpret_cast<uint4*>(ry + 2 * x0) = w;
-      }
+      if (OUT8) *reinterpret_cast<uint2*>(ry + x0) = pack_codes<true>(yo[j]);
+      else *reinterpret_cast<uint4*>(ry + 2 * x0) = pack_codes<false>(yo[j]);
     } else {
 #pragma unroll
       for (int k = 0; k < 2 * QPT; k++) {
@@ -252,33 +237,16 @@ __global__ __launch_bounds__(256) void k_process(const KParams P0) {
   uint8_t* ru = P.out[1] + f * P.out_fp[1] + cy * P.out_ls[1];
   uint8_t* rv = P.out[2] + f * P.out_fp[2] + cy * P.out_ls[2];
   if (VEC && full && QPT == 4 && P.out_cstep == 2) {   // semi-planar: the four (Cb, Cr) pairs in one store
-    if (OUT8) {
-      uint2 a;
-      a.x = (unsigned)uo[0] | ((unsigned)vo[0] << 8) | ((unsigned)uo[1] << 16) | ((unsigned)vo[1] << 24);
-      a.y = (unsigned)uo[2] | ((unsigned)vo[2] << 8) | ((unsigned)uo[3] << 16) | ((unsigned)vo[3] << 24);
-      *reinterpret_cast<uint2*>(ru + 2 * cx0) = a;
-    } else {
-      uint4 a;
-      a.x = (unsigned)uo[0] | ((unsigned)vo[0] << 16);
-      a.y = (unsigned)uo[1] | ((unsigned)vo[1] << 16);
-      a.z = (unsigned)uo[2] | ((unsigned)vo[2] << 16);
-      a.w = (unsigned)uo[3] | ((unsigned)vo[3] << 16);
-      *reinterpret_cast<uint4*>(ru + 4 * cx0) = a;
-    }
+    const int uv[8] = {uo[0], vo[0], uo[1], vo[1], uo[2], vo[2], uo[3], vo[3]};
+    if (OUT8) *reinterpret_cast<uint2*>(ru + 2 * cx0) = pack_codes<true>(uv);
+    else *reinterpret_cast<uint4*>(ru + 4 * cx0) = pack_codes<false>(uv);
   } else if (VEC && full && QPT == 4) {
     if (OUT8) {
-      *reinterpret_cast<unsigned*>(ru + cx0) =
-          (unsigned)uo[0] | ((unsigned)uo[1] << 8) | ((unsigned)uo[2] << 16) | ((unsigned)uo[3] << 24);
-      *reinterpret_cast<unsigned*>(rv + cx0) =
-          (unsigned)vo[0] | ((unsigned)vo[1] << 8) | ((unsigned)vo[2] << 16) | ((unsigned)vo[3] << 24);
+      *reinterpret_cast<unsigned*>(ru + cx0) = pack_codes<true>(uo);
+      *reinterpret_cast<unsigned*>(rv + cx0) = pack_codes<true>(vo);
     } else {
-      uint2 a, b;
-      a.x = (unsigned)uo[0] | ((unsigned)uo[1] << 16);
-      a.y = (unsigned)uo[2] | ((unsigned)uo[3] << 16);
-      b.x = (unsigned)vo[0] | ((unsigned)vo[1] << 16);
-      b.y = (unsigned)vo[2] | ((unsigned)vo[3] << 16);
-      *reinterpret_cast<uint2*>(ru + 2 * cx0) = a;
-      *reinterpret_cast<uint2*>(rv + 2 * cx0) = b;
+      *reinterpret_cast<uint2*>(ru + 2 * cx0) = pack_codes<false>(uo);
+      *reinterpret_cast<uint2*>(rv + 2 * cx0) = pack_codes<false>(vo);
     }
   } else {
 #pragma unroll
@@ -452,28 +420,24 @@ hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s) {
+template <bool DOVI>
+static hipError_t launch_debug_stage(const KParams& P, int stage, float* out, hipStream_t s) {
   const long long npx = (long long)P.W * P.H;
   dim3 grid((unsigned)((npx + 255) / 256)), block(256);
-  if (P.dovi) {   // frame 0's Dolby Vision record (libplacebo pipeline only: check_dovi)
-    if (P.pipe != PIPE_LIBPLACEBO || P.sub || P.vco) return hipErrorInvalidValue;
-    switch (stage) {
-      case 1: hipLaunchKernelGGL((k_debug<1, true>), grid, block, 0, s, P, out); break;
-      case 2: hipLaunchKernelGGL((k_debug<2, true>), grid, block, 0, s, P, out); break;
-      case 3: hipLaunchKernelGGL((k_debug<3, true>), grid, block, 0, s, P, out); break;
-      case 4: hipLaunchKernelGGL((k_debug<4, true>), grid, block, 0, s, P, out); break;
-      default: hipLaunchKernelGGL((k_debug<5, true>), grid, block, 0, s, P, out); break;
-    }
-    return hipGetLastError();
-  }
   switch (stage) {
-    case 1: hipLaunchKernelGGL((k_debug<1>), grid, block, 0, s, P, out); break;
-    case 2: hipLaunchKernelGGL((k_debug<2>), grid, block, 0, s, P, out); break;
-    case 3: hipLaunchKernelGGL((k_debug<3>), grid, block, 0, s, P, out); break;
-    case 4: hipLaunchKernelGGL((k_debug<4>), grid, block, 0, s, P, out); break;
-    default: hipLaunchKernelGGL((k_debug<5>), grid, block, 0, s, P, out); break;
+    case 1: hipLaunchKernelGGL((k_debug<1, DOVI>), grid, block, 0, s, P, out); break;
+    case 2: hipLaunchKernelGGL((k_debug<2, DOVI>), grid, block, 0, s, P, out); break;
+    case 3: hipLaunchKernelGGL((k_debug<3, DOVI>), grid, block, 0, s, P, out); break;
+    case 4: hipLaunchKernelGGL((k_debug<4, DOVI>), grid, block, 0, s, P, out); break;
+    default: hipLaunchKernelGGL((k_debug<5, DOVI>), grid, block, 0, s, P, out); break;
   }
   return hipGetLastError();
+}
+
+hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s) {
+  // frame 0's Dolby Vision record (libplacebo pipeline only: check_dovi)
+  if (P.dovi && (P.pipe != PIPE_LIBPLACEBO || P.sub || P.vco)) return hipErrorInvalidValue;
+  return P.dovi ? launch_debug_stage<true>(P, stage, out, s) : launch_debug_stage<false>(P, stage, out, s);
 }
 
 // BICUBIC chroma, pass 2: the decimation of one frame's chr444
@@ -484,527 +448,6 @@ hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float
   const unsigned nc = (unsigned)(((long long)P.cw * P.ch + 255) / 256);
   if (out8) hipLaunchKernelGGL((k_chroma_bicubic<true>), dim3(nc), dim3(256), 0, s, P, T);
   else hipLaunchKernelGGL((k_chroma_bicubic<false>), dim3(nc), dim3(256), 0, s, P, T);
-  return hipGetLastError();
-}
-
-// ---- dynamic peak statistics (params.peak_detect, BT.2390) -----------------
-// Per frame, the maximum and the sum of the PQ-encoded max(R,G,B) of every
-// pixel (libplacebo peak detection, src/utils.py:448; PARITY UNPINNED: no
-// libplacebo here, model in DESIGN.md).  PQ sources: PQ(max(EOTF(E))) ==
-// clamp(max(E), 0, 1) exactly, so no transcendental is needed.  Chroma is
-// taken nearest (the statistic is an estimate).  grid = (M.nblocks, frames);
-// partial[f * M.nblocks + b] = (max, sum) over block b's rows / chunks
-// one pixel's PQ-domain max(R,G,B) from its integer codes (nearest chroma)
-// TRC 2: a Dolby Vision profile-5 frame (R: its record, h2s_set_dovi): the
-// front-end's linear BT.2020 light (h2s_dovi.h, float32; 1 = 10000 nits),
-// PQ-encoded; no shortcut, since max(Lm lms) is not the largest L'M'S'
-// DoviStat: what a block's pixels share (hoisted out of the row loop by
-// k_peak_stats: block-uniform): 1 / (2^b - 1) and the record's linear matrix
-struct DoviStat {
-  float inv, lin[9];
-};
-template <int TRC>
-__device__ __forceinline__ float peak_px(const KParams& P, unsigned yc, unsigned uc, unsigned vc,
-                                         const DoviRec* R = nullptr, const DoviStat* S = nullptr) {
-  yc = (yc >> P.in_sh) & P.in_mask, uc = (uc >> P.in_sh) & P.in_mask, vc = (vc >> P.in_sh) & P.in_mask;   // code_of
-  if constexpr (TRC == 2) {
-    // (model step 1's clamp to [0, 1] is no operation here: in_mask bounds every code by 2^b - 1)
-    const float sv[3] = {(float)yc * S->inv, (float)uc * S->inv, (float)vc * S->inv};
-    float v[3];
-    dovi_lms_pq<float>(*R, sv, v);
-    const float l[3] = {pq_eotf(v[0]), pq_eotf(v[1]), pq_eotf(v[2])};
-    const float r = S->lin[0] * l[0] + S->lin[1] * l[1] + S->lin[2] * l[2];
-    const float g = S->lin[3] * l[0] + S->lin[4] * l[1] + S->lin[5] * l[2];
-    const float bl = S->lin[6] * l[0] + S->lin[7] * l[1] + S->lin[8] * l[2];
-    // the linear matrix may leave every channel negative: such a pixel counts as black (PQ(0), as
-    // pq_encode's own max(y, 0) would give; stated here rather than left to it)
-    return clamp01(pq_encode(fmaxf(fmaxf(fmaxf(r, g), bl), 0.0f)));
-  }
-  const float Y = (float)yc * P.y_scale + P.y_off;
-  const float cb = (float)uc * P.c_scale + P.c_off, cr = (float)vc * P.c_scale + P.c_off;
-  const float er = Y + P.m_rcr * cr, eg = Y + P.m_gcb * cb + P.m_gcr * cr, eb = Y + P.m_bcb * cb;
-  if (TRC == 0) return clamp01(fmaxf(fmaxf(er, eg), eb));
-  const float r = hlg_inv_oetf(er), g = hlg_inv_oetf(eg), bl = hlg_inv_oetf(eb);
-  const float ys = 0.2627f * r + 0.6780f * g + 0.0593f * bl;
-  const float w = ys > 0.0f ? P.lin_scale * apow(ys, 0.2f) : 0.0f;
-  return clamp01(pq_encode(fmaxf(fmaxf(r, g), bl) * w * P.npl_1e4));
-}
-
-// percentile model (pd_percentile < 100; PARITY UNPINNED):
-// a PEAK_BINS-bin histogram of the per-pixel PQ(max R,G,B) per frame; the
-// percentile is interpolated inside its bin by k_peak_frame (oracle_peak_stats)
-// a thread's run of equal bins, added to the LDS histogram once per run: on
-// smooth content neighbouring pixels share a bin, and one LDS atomic per pixel
-// had all 64 lanes of a wave serialise on one address; the
-// counts are the same, only the number of atomics changes
-struct HistRun {
-  int bin = -1;
-  unsigned n = 0;
-  __device__ __forceinline__ void add(unsigned* lh, float m) {
-    const int b = min((int)(m * (float)PEAK_BINS), PEAK_BINS - 1);
-    if (b != bin) {
-      if (n) atomicAdd(&lh[bin], n);
-      bin = b, n = 0;
-    }
-    n++;
-  }
-  // n values of bin b (a whole quad-form unit in one step)
-  __device__ __forceinline__ void add_n(unsigned* lh, int b, unsigned k) {
-    if (b != bin) {
-      if (n) atomicAdd(&lh[bin], n);
-      bin = b, n = 0;
-    }
-    n += k;
-  }
-  __device__ __forceinline__ void flush(unsigned* lh) {
-    if (n) atomicAdd(&lh[bin], n);
-    n = 0;
-  }
-};
-__device__ __forceinline__ void hist_flush(const unsigned* lh, unsigned* hist) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < PEAK_BINS; i += 256)
-    if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
-// block (max, sum) reduction; thread 0 writes the record
-__device__ __forceinline__ void peak_reduce(float mx, float sm, float2* out) {
-  __shared__ float smx[256], ssm[256];
-  smx[threadIdx.x] = mx, ssm[threadIdx.x] = sm;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + o]);
-      ssm[threadIdx.x] += ssm[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = make_float2(smx[0], ssm[0]);
-}
-
-// ---- dynamic peak: per-frame statistic and curve records on the device ----
-// One frame's (PQ peak measurement, average PQ) from its nblocks partial
-// (max, sum) records and, for pd_percentile < 100, the percentile from the
-// frame's histogram: the first bin whose cumulative count reaches pct % of
-// the pixels, interpolated linearly inside it, capped at the frame maximum
-// (oracle_peak_stats).  Wave-level reductions and scans (no LDS tree): the
-// records fold in a fixed pairwise order in double (deterministic, so sharded
-// and sequential statistics stay bit-identical), the counts are integers (a
-// u32 scan equals a serial accumulation exactly).  The histogram is left
-// zeroed for the next call.  256 threads.
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ void peak_frame_fold(const float2* partial, unsigned* hist, const PeakModel& M, double2* fstat, int f) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  __shared__ double s_sum[4];
-  __shared__ float s_mx[4];
-  __shared__ unsigned s_wtot[4];
-  __shared__ int s_bin;
-  static_assert(PEAK_BLOCKS_MAX <= 256, "one partial record per thread");
-  const float2 rec = t < M.nblocks ? partial[(size_t)f * M.nblocks + t] : make_float2(0.0f, 0.0f);
-  const double ws = wave_sum_d((double)rec.y);
-  const float wm = wave_max_f(rec.x);
-  if (lane == 0) s_sum[w] = ws, s_mx[w] = wm;
-  if (t == 0) s_bin = PEAK_BINS;
-  unsigned cnt[4] = {0u, 0u, 0u, 0u}, incl = 0u;
-  if (M.pct) {
-    static_assert(PEAK_BINS == 4 * 256, "four bins per thread");
-    uint4* h = reinterpret_cast<uint4*>(hist + (size_t)f * PEAK_BINS);
-    const uint4 c = h[t];
-    h[t] = make_uint4(0u, 0u, 0u, 0u);
-    cnt[0] = c.x, cnt[1] = c.y, cnt[2] = c.z, cnt[3] = c.w;
-    incl = c.x + c.y + c.z + c.w;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {   // inclusive scan within the wave
-      const unsigned v = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_wtot[w] = incl;
-  }
-  __syncthreads();
-  const double sum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-  const double mx = (double)fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-  if (M.pct) {
-    unsigned before = 0u, n = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      before += k < w ? s_wtot[k] : 0u;
-      n += s_wtot[k];
-    }
-    const double target = M.percentile / 100.0 * (double)n;
-    double cum = (double)(before + incl - (cnt[0] + cnt[1] + cnt[2] + cnt[3]));
-    int mine = PEAK_BINS;
-    double cum_at = 0.0;
-    for (int k = 0; k < 4; k++) {
-      if (mine == PEAK_BINS && cnt[k] && cum + cnt[k] >= target) mine = 4 * t + k, cum_at = cum;
-      cum += cnt[k];
-    }
-    if (mine < PEAK_BINS) atomicMin(&s_bin, mine);
-    __syncthreads();
-    if (mine < PEAK_BINS && mine == s_bin) {   // the owner of the first bin
-      const double v = (mine + (target - cum_at) / cnt[mine & 3]) / PEAK_BINS;
-      fstat[f] = make_double2(v < mx ? v : mx, sum / M.npx);
-    } else if (t == 0 && s_bin == PEAK_BINS) {
-      fstat[f] = make_double2(mx, sum / M.npx);
-    }
-  } else if (t == 0) {
-    fstat[f] = make_double2(mx, sum / M.npx);
-  }
-}
-
-// The IIR over n frames in order (thread 0, from the state the previous calls
-// left in *st), then each frame's peak and curve record in parallel.
-// out = null: the state only.  Every thread of the block calls it.  The
-// frames' statistics are staged through LDS, PEAK_IIR_CHUNK at a time, so
-// the serial recurrence reads LDS instead of making a global round trip per
-// frame (its loads could not be hoisted past the stores of the smoothed
-// values: finish 20.8 -> see DESIGN.md §4.6)
-constexpr int PEAK_IIR_CHUNK = 1024;
-__device__ void peak_curves_body(double2* fstat, int n, const PeakModel& M, PeakState* st, CurveConsts* out) {
-  const int t = threadIdx.x;
-  __shared__ double2 s_f[PEAK_IIR_CHUNK];
-  __shared__ PeakState s_st;
-  if (t == 0) s_st = *st;
-  for (int c0 = 0; c0 < n; c0 += PEAK_IIR_CHUNK) {
-    const int cn = n - c0 < PEAK_IIR_CHUNK ? n - c0 : PEAK_IIR_CHUNK;
-    __syncthreads();
-    for (int f = t; f < cn; f += blockDim.x) s_f[f] = fstat[c0 + f];
-    __syncthreads();
-    if (t == 0) {
-      PeakState s = s_st;
-      for (int f = 0; f < cn; f++) {
-        peak_iir_step(&s, M, s_f[f].x, s_f[f].y);
-        s_f[f] = make_double2(s.max, s.avg);   // the smoothed values frame f's curve uses
-      }
-      s_st = s;
-    }
-    __syncthreads();
-    for (int f = t; f < cn; f += blockDim.x) {
-      fstat[c0 + f] = s_f[f];
-      const double pk = peak_of(M, s_f[f].x);
-      if (c0 + f == n - 1) s_st.peak = pk;    // the state's peak: the last frame's (its smoothed max)
-      if (out) curve_for_peak(M, pk, s_f[f].y, &out[c0 + f]);
-    }
-  }
-  __syncthreads();
-  if (t == 0) *st = s_st;
-}
-
-// k_peak_finish: one block per frame folds that frame's records (and clears
-// its histogram for the next call); the last frame to finish (a device-scope
-// counter after a release fence: one per frame, so the fences stay few) runs
-// the IIR and the curve records for all of the launch's frames.  PeakTail
-// (h2s_peak.h) names the buffers; the counter is zeroed by the statistics
-// launch queued before every finish launch (so an aborted launch cannot
-// leave it stale) and left zero.
-__global__ __launch_bounds__(256) void k_peak_finish(const float2* partial, const PeakTail T) {
-  const int f = blockIdx.x;
-  __shared__ int s_last;
-  peak_frame_fold(partial, T.hist, T.M, T.fstat, f);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();   // fstat[f] and the cleared histogram, device-wide
-    s_last = atomicAdd(T.done, 1u) == (unsigned)T.nframes - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  if (threadIdx.x == 0) *T.done = 0u;
-  if (T.st) peak_curves_body(T.fstat, T.nframes, T.M, T.st, T.out);
-}
-
-// generic form: any width / alignment, 2-byte loads
-template <int TRC, bool HIST>
-__global__ __launch_bounds__(256) void k_peak_stats(const KParams P, float2* partial, const PeakTail T) {
-  __shared__ unsigned lh[HIST ? PEAK_BINS : 1];
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *T.done = 0u;   // k_peak_finish's counter (stream-ordered)
-  if (HIST)
-    for (int i = threadIdx.x; i < PEAK_BINS; i += 256) lh[i] = 0;
-  if (HIST) __syncthreads();
-  const int f = blockIdx.y, b = blockIdx.x;
-  const DoviRec* const rec = TRC == 2 ? dovi_record(P, f) : nullptr;   // (block-uniform: one frame per block)
-  DoviStat ds;
-  if constexpr (TRC == 2) {
-    ds.inv = 1.0f / (float)((256 << P.x_sh) - 1);
-    for (int i = 0; i < 9; i++) ds.lin[i] = rec->lin[i];
-  }
-  float mx = 0.0f, sm = 0.0f;
-  HistRun run;
-  for (int y = b; y < P.H; y += gridDim.x) {
-    const uint16_t* yr = reinterpret_cast<const uint16_t*>(P.in[0] + f * P.in_fp[0] + y * P.in_ls[0]);
-    const uint16_t* ur = reinterpret_cast<const uint16_t*>(P.in[1] + f * P.in_fp[1] + (y >> 1) * P.in_ls[1]);
-    const uint16_t* vr = reinterpret_cast<const uint16_t*>(P.in[2] + f * P.in_fp[2] + (y >> 1) * P.in_ls[2]);
-    float rs = 0.0f;
-    for (int x = threadIdx.x; x < P.W; x += blockDim.x) {
-      const int xc = (x >> 1) * P.in_cstep;   // (semi-planar: vr = ur + 1, pairs two words apart)
-      const float m = peak_px<TRC>(P, yr[x], ur[xc], vr[xc], rec, &ds);
-      mx = fmaxf(mx, m);
-      rs += m;
-      if (HIST) run.add(lh, m);
-    }
-    sm += rs;
-  }
-  if (HIST) run.flush(lh);
-  if (HIST) hist_flush(lh, T.hist + (size_t)f * PEAK_BINS);
-  peak_reduce(mx, sm, &partial[f * gridDim.x + b]);
-}
-
-// streaming form (W % 8 == 0, 16-byte luma / 8-byte chroma alignment): each
-// thread takes 8-pixel row chunks (one 16-byte luma load, one 8-byte load per
-// chroma plane), four chunks' loads in flight.  The round-5 default; the A/B
-// reference of the quad form below (H2S_OPT_TEST_PEAK_FORM 1) and the form
-// for HLG input
-#ifndef H2S_PEAK_INFLIGHT
-#define H2S_PEAK_INFLIGHT 4
-#endif
-template <int TRC, bool HIST>
-__global__ __launch_bounds__(256) void k_peak_stats_v(const KParams P, float2* partial, const PeakTail T) {
-  __shared__ unsigned lh[HIST ? PEAK_BINS : 1];
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *T.done = 0u;   // k_peak_finish's counter (stream-ordered)
-  if (HIST)
-    for (int i = threadIdx.x; i < PEAK_BINS; i += 256) lh[i] = 0;
-  if (HIST) __syncthreads();
-  const int f = blockIdx.y;
-  const int cpr = P.W >> 3;                       // chunks per row
-  const int nch = P.H * cpr, stride = gridDim.x * 256;
-  const uint8_t* y0 = P.in[0] + f * P.in_fp[0];
-  const uint8_t* u0 = P.in[1] + f * P.in_fp[1];
-  const uint8_t* v0 = P.in[2] + f * P.in_fp[2];
-  float mx = 0.0f, sm = 0.0f;
-  HistRun run;
-  struct Chunk {
-    uint4 ya;
-    uint2 ua, va;
-  };
-  auto load = [&](int i, Chunk& c) {
-    const int r = i / cpr, cx = i - r * cpr;
-    c.ya = reinterpret_cast<const uint4*>(y0 + r * P.in_ls[0])[cx];
-    if (P.in_cstep == 2) {   // semi-planar: the chunk's four (Cb, Cr) pairs, 16 bytes of plane 1
-      const uint2* q = reinterpret_cast<const uint2*>(u0 + (r >> 1) * P.in_ls[1]) + 2 * cx;
-      c.ua = q[0], c.va = q[1];
-    } else {
-      c.ua = reinterpret_cast<const uint2*>(u0 + (r >> 1) * P.in_ls[1])[cx];
-      c.va = reinterpret_cast<const uint2*>(v0 + (r >> 1) * P.in_ls[2])[cx];
-    }
-  };
-  auto fold = [&](const Chunk& c) {
-    unsigned uu[4] = {c.ua.x & 0xffff, c.ua.x >> 16, c.ua.y & 0xffff, c.ua.y >> 16};
-    unsigned vv[4] = {c.va.x & 0xffff, c.va.x >> 16, c.va.y & 0xffff, c.va.y >> 16};
-    if (P.in_cstep == 2) {   // pairs: word k = (Cb k, Cr k)
-      const unsigned w[4] = {c.ua.x, c.ua.y, c.va.x, c.va.y};
-#pragma unroll
-      for (int k = 0; k < 4; k++) uu[k] = w[k] & 0xffff, vv[k] = w[k] >> 16;
-    }
-    const unsigned yy[8] = {c.ya.x & 0xffff, c.ya.x >> 16, c.ya.y & 0xffff, c.ya.y >> 16,
-                            c.ya.z & 0xffff, c.ya.z >> 16, c.ya.w & 0xffff, c.ya.w >> 16};
-    float rs = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const float m = peak_px<TRC>(P, yy[k], uu[k >> 1], vv[k >> 1]);
-      mx = fmaxf(mx, m);
-      rs += m;
-      if (HIST) run.add(lh, m);
-    }
-    sm += rs;
-  };
-  int i = blockIdx.x * 256 + threadIdx.x;
-  for (; i + (H2S_PEAK_INFLIGHT - 1) * stride < nch; i += H2S_PEAK_INFLIGHT * stride) {
-    Chunk c[H2S_PEAK_INFLIGHT];
-#pragma unroll
-    for (int k = 0; k < H2S_PEAK_INFLIGHT; k++) load(i + k * stride, c[k]);
-#pragma unroll
-    for (int k = 0; k < H2S_PEAK_INFLIGHT; k++) fold(c[k]);
-  }
-  for (; i < nch; i += stride) {
-    Chunk c;
-    load(i, c);
-    fold(c);
-  }
-  if (HIST) run.flush(lh);
-  if (HIST) hist_flush(lh, T.hist + (size_t)f * PEAK_BINS);
-  peak_reduce(mx, sm, &partial[f * gridDim.x + blockIdx.x]);
-}
-
-// quad form, the default for PQ input (W % 16 == 0, 16-byte rows; VERDICT
-// r05 item 4): a thread's unit is 32 pixels -- 16 columns of a luma row pair
-// and their 8 chroma samples -- read as six 16-byte loads (no chroma row read
-// twice), two units' loads in flight.  PQ(max EOTF(R'G'B')) = clamp(max E):
-// the chroma terms are maximised once per chroma sample (with Y's offset:
-// d = y_off + max(a_rv v, a_gu u + a_gv v, a_bu u)) and each pixel is one FMA
-// clamped to [0, 1] (E = code ys + d).  The histogram (pd_percentile < 100)
-// takes a whole unit in one run step when the unit's smallest and largest
-// values share a bin (bin() is monotonic: 55 % of the website frame's units);
-// a unit that spans bins -- on the bench content 94 % of units span 8 or more
-//  -- adds each value with its own LDS atomic, no run
-// bookkeeping, the bin index floor(1024 m) unclamped into a 1025th entry (m =
-// 1 exactly) folded into the last bin before the flush.  Every sum runs in a fixed
-// order within the frame (unit by unit, 32 pixels row by row), so sharded
-// and sequential statistics stay bit-identical.
-template <bool HIST, int INF = 2>   // INF: units whose loads are in flight (4: A/B, H2S_OPT_TEST_PEAK_FORM 2)
-__global__ __launch_bounds__(256) void k_peak_stats_q(const KParams P, float2* partial, const PeakTail T) {
-  __shared__ unsigned lh[HIST ? PEAK_BINS + 1 : 1];   // + the bin of m = 1 exactly, folded into the last at the end
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *T.done = 0u;   // k_peak_finish's counter (stream-ordered)
-  if (HIST)
-    for (int i = threadIdx.x; i <= PEAK_BINS; i += 256) lh[i] = 0;
-  if (HIST) __syncthreads();
-  const int f = blockIdx.y;
-  const int cpr = P.W >> 4, nch = (P.H >> 1) * cpr, stride = gridDim.x * 256;
-  const uint8_t* y0 = P.in[0] + f * P.in_fp[0];
-  const uint8_t* u0 = P.in[1] + f * P.in_fp[1];
-  const uint8_t* v0 = P.in[2] + f * P.in_fp[2];
-  const unsigned m2 = P.in_mask | (P.in_mask << 16);
-  const int sh = P.in_sh;   // semi-planar: codes in the words' high bits (m2 clears what crosses the halves)
-  const float ys = P.y_scale, yo = P.y_off, cs = P.c_scale, co = P.c_off;
-  float mx = 0.0f, sm = 0.0f;
-  HistRun run;
-  struct Unit {
-    uint4 u, v, y0a, y0b, y1a, y1b;
-  };
-  auto load = [&](int i, Unit& q) {
-    const int r = i / cpr, cx = i - r * cpr;
-    if (P.in_cstep == 2) {   // semi-planar: the unit's eight (Cb, Cr) pairs, 32 bytes of plane 1
-      q.u = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 32 * cx);
-      q.v = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 32 * cx + 16);
-    } else {
-      q.u = *reinterpret_cast<const uint4*>(u0 + r * P.in_ls[1] + 16 * cx);
-      q.v = *reinterpret_cast<const uint4*>(v0 + r * P.in_ls[2] + 16 * cx);
-    }
-    const uint4* ya = reinterpret_cast<const uint4*>(y0 + 2 * r * P.in_ls[0] + 32 * cx);
-    const uint4* yb = reinterpret_cast<const uint4*>(y0 + (2 * r + 1) * P.in_ls[0] + 32 * cx);
-    q.y0a = ya[0], q.y0b = ya[1], q.y1a = yb[0], q.y1b = yb[1];
-  };
-  // the 32 values of a unit, in order, to fn(m)
-  auto each = [&](const Unit& q, const float (&d)[8], auto&& fn) {
-    const uint4 rows[4] = {q.y0a, q.y0b, q.y1a, q.y1b};
-#pragma unroll
-    for (int h = 0; h < 4; h++) {
-      const unsigned w[4] = {(rows[h].x >> sh) & m2, (rows[h].y >> sh) & m2, (rows[h].z >> sh) & m2, (rows[h].w >> sh) & m2};
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const unsigned code = (k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xffffu;
-        fn(__builtin_amdgcn_fmed3f(fmaf((float)code, ys, d[4 * (h & 1) + (k >> 1)]), 0.0f, 1.0f));
-      }
-    }
-  };
-  auto fold = [&](const Unit& q) {
-    unsigned ua[4] = {(q.u.x >> sh) & m2, (q.u.y >> sh) & m2, (q.u.z >> sh) & m2, (q.u.w >> sh) & m2};
-    unsigned va[4] = {(q.v.x >> sh) & m2, (q.v.y >> sh) & m2, (q.v.z >> sh) & m2, (q.v.w >> sh) & m2};
-    if (P.in_cstep == 2) {   // pairs (word k = Cb k | Cr k << 16) -> the planar words (block-uniform)
-      const unsigned p[8] = {ua[0], ua[1], ua[2], ua[3], va[0], va[1], va[2], va[3]};
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        ua[i] = (p[2 * i] & 0xffffu) | (p[2 * i + 1] << 16);
-        va[i] = (p[2 * i] >> 16) | (p[2 * i + 1] & 0xffff0000u);
-      }
-    }
-    float d[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const float cb = fmaf((float)((j & 1) ? ua[j >> 1] >> 16 : ua[j >> 1] & 0xffffu), cs, co);
-      const float cr = fmaf((float)((j & 1) ? va[j >> 1] >> 16 : va[j >> 1] & 0xffffu), cs, co);
-      d[j] = yo + fmaxf(fmaxf(P.m_rcr * cr, fmaf(P.m_gcb, cb, P.m_gcr * cr)), P.m_bcb * cb);
-    }
-    float rs = 0.0f, umx = 0.0f, umn = 1.0f;
-    each(q, d, [&](float m) {
-      umx = fmaxf(umx, m);
-      umn = fminf(umn, m);
-      rs += m;
-    });
-    mx = fmaxf(mx, umx);
-    sm += rs;
-    if (HIST) {
-      const int b0 = min((int)(umn * (float)PEAK_BINS), PEAK_BINS - 1);
-      const int b1 = min((int)(umx * (float)PEAK_BINS), PEAK_BINS - 1);
-      if (b0 == b1) {
-        run.add_n(lh, b0, 32u);
-      } else {
-        each(q, d, [&](float m) { atomicAdd(&lh[(unsigned)(m * (float)PEAK_BINS)], 1u); });
-      }
-    }
-  };
-  int i = blockIdx.x * 256 + threadIdx.x;
-  for (; i + (INF - 1) * stride < nch; i += INF * stride) {
-    Unit q[INF];
-#pragma unroll
-    for (int k = 0; k < INF; k++) load(i + k * stride, q[k]);
-#pragma unroll
-    for (int k = 0; k < INF; k++) fold(q[k]);
-  }
-  for (; i < nch; i += stride) {
-    Unit q;
-    load(i, q);
-    fold(q);
-  }
-  if (HIST) {
-    run.flush(lh);
-    __syncthreads();
-    if (threadIdx.x == 0) lh[PEAK_BINS - 1] += lh[PEAK_BINS];
-    hist_flush(lh, T.hist + (size_t)f * PEAK_BINS);
-  }
-  peak_reduce(mx, sm, &partial[f * gridDim.x + blockIdx.x]);
-}
-
-// the statistics of P's frames, then (k_peak_finish) their (measurement,
-// average) in T.fstat and, T.st set, the smoothed state and curve records:
-// two launches
-hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& T, hipStream_t s) {
-  if (P.nframes <= 0) return hipSuccess;
-  const dim3 grid(T.M.nblocks, P.nframes);
-  auto al = [](long long v, int a) { return (v & (a - 1)) == 0; };
-  // (semi-planar: plane 2 is plane 1 one sample on, and is not loaded from)
-  auto planes_al = [&](int ya, int ca) {
-    return al((long long)(uintptr_t)P.in[0], ya) && al(P.in_ls[0], ya) && al(P.in_fp[0], ya) &&
-           al((long long)(uintptr_t)P.in[1], ca) && al(P.in_ls[1], ca) && al(P.in_fp[1], ca) &&
-           (P.in_cstep == 2 ||
-            (al((long long)(uintptr_t)P.in[2], ca) && al(P.in_ls[2], ca) && al(P.in_fp[2], ca)));
-  };
-  const bool vec = P.W % 8 == 0 && planes_al(16, 8);
-  const bool quad = P.W % 16 == 0 && P.transfer == 0 && T.form != 1 && planes_al(16, 16);
-  // (a Dolby Vision set, P.dovi: the generic row form, whatever the rows allow)
-#define H2S_PEAK_LAUNCH(HI)                                                                   \
-  if (P.dovi)                                                                                 \
-    hipLaunchKernelGGL((k_peak_stats<2, HI>), grid, dim3(256), 0, s, P, partial, T);          \
-  else if (quad && T.form == 2)                                                               \
-    hipLaunchKernelGGL((k_peak_stats_q<HI, 4>), grid, dim3(256), 0, s, P, partial, T);        \
-  else if (quad)                                                                              \
-    hipLaunchKernelGGL((k_peak_stats_q<HI>), grid, dim3(256), 0, s, P, partial, T);           \
-  else if (vec && P.transfer == 1)                                                            \
-    hipLaunchKernelGGL((k_peak_stats_v<1, HI>), grid, dim3(256), 0, s, P, partial, T);        \
-  else if (vec)                                                                               \
-    hipLaunchKernelGGL((k_peak_stats_v<0, HI>), grid, dim3(256), 0, s, P, partial, T);        \
-  else if (P.transfer == 1)                                                                   \
-    hipLaunchKernelGGL((k_peak_stats<1, HI>), grid, dim3(256), 0, s, P, partial, T);          \
-  else                                                                                        \
-    hipLaunchKernelGGL((k_peak_stats<0, HI>), grid, dim3(256), 0, s, P, partial, T);
-  if (T.M.pct) {
-    H2S_PEAK_LAUNCH(true)
-  } else {
-    H2S_PEAK_LAUNCH(false)
-  }
-#undef H2S_PEAK_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_peak_finish, dim3(P.nframes), dim3(256), 0, s, partial, T);
-  return hipGetLastError();
-}
-
-// h2s_peak_feed: the IIR over caller-supplied statistics.  One block
-void __global__ __launch_bounds__(64) k_peak_curves(double2* fstat, int n, const PeakModel M, PeakState* st,
-                                                    CurveConsts* out) {
-  peak_curves_body(fstat, n, M, st, out);
-}
-
-hipError_t launch_peak_curves(double2* fstat, int n, const PeakModel& M, PeakState* st, CurveConsts* out,
-                              hipStream_t s) {
-  hipLaunchKernelGGL(k_peak_curves, dim3(1), dim3(64), 0, s, fstat, n, M, st, out);
   return hipGetLastError();
 }
 
@@ -1042,58 +485,4 @@ hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s) {
   hipLaunchKernelGGL(k_build_lut8x, dim3((1u << 24) / 256), dim3(256), 0, s, P, out);
   return hipGetLastError();
 }
-
-// device libm_powf / libm_expf over n inputs (fn 0: powf(x, y), 1: expf(x)),
-// for tests/test_libm_tables.py's bit-equality check against the libm the
-// oracle links
-__global__ void k_test_libm(int fn, const float* x, const float* y, float* out, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = fn == 0 ? libm_powf(x[i], y[i]) : libm_expf(x[i]);
-}
-
 }  // namespace h2s
-
-// Private test entry (not part of the C-ABI, not declared in include/h2s.h):
-// host arrays in and out, synchronous, on the current device.  Returns 0 or
-// a negative HIP error.
-extern "C" __attribute__((visibility("default"))) int h2stest_libm(int fn, const float* x, const float* y, float* out,
-                                                                    int n) {
-  if (n <= 0) return 0;
-  float* d = nullptr;
-  const size_t b = (size_t)n * sizeof(float);
-  if (hipMalloc(&d, 3 * b) != hipSuccess) return -1;
-  hipError_t e = hipMemcpy(d, x, b, hipMemcpyHostToDevice);
-  if (e == hipSuccess && y) e = hipMemcpy(d + n, y, b, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(h2s::k_test_libm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, d, d + n, d + 2 * n, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * n, b, hipMemcpyDeviceToHost);
-  hipFree(d);
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
-// private test hook (not in include/h2s.h): the libplacebo branch's lut3d
-// 8-bit table (k_build_lut8x) for a host lattice of n^3 R'G'B' records (3
-// floats each, r fastest), copied back in the kernel's bit-interleaved
-// order (2^24 u32).  For tests/test_gpu_parity.py's whole-table comparison
-// with the oracle's lut3d 8-bit path.  Returns 0 or a negative HIP error.
-extern "C" __attribute__((visibility("default"))) int h2stest_lut8x(const float* lut_rgb, int n, unsigned* out) {
-  if (n < 2 || n > 256) return -1;
-  const size_t nn = (size_t)n * n * n;
-  std::vector<float4> l4(nn + 1, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  for (size_t i = 0; i < nn; i++) l4[i] = make_float4(lut_rgb[3 * i], lut_rgb[3 * i + 1], lut_rgb[3 * i + 2], 0.0f);
-  float4* dl = nullptr;
-  unsigned* dt = nullptr;
-  if (hipMalloc(&dl, l4.size() * sizeof(float4)) != hipSuccess) return -1;
-  if (hipMalloc(&dt, sizeof(unsigned) << 24) != hipSuccess) {
-    hipFree(dl);
-    return -1;
-  }
-  hipError_t e = hipMemcpy(dl, l4.data(), l4.size() * sizeof(float4), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = h2s::build_lut8x(dl, n, dt, 0);
-  if (e == hipSuccess) e = hipMemcpy(out, dt, sizeof(unsigned) << 24, hipMemcpyDeviceToHost);
-  hipFree(dl);
-  hipFree(dt);
-  return e == hipSuccess ? 0 : -(int)e;
-}

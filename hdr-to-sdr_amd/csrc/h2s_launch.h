@@ -1,6 +1,7 @@
 // h2s_launch.h — the one declaration of every host-callable kernel launcher.
-// Included by the unit that defines a launcher (h2s_kernels.hip, h2s_fast.hip,
-// h2s_preview.hip) and by every host unit that calls one, so a signature or an
+// Included by the unit that defines a launcher (h2s_kernels.hip, h2s_peak.hip,
+// h2s_fast.hip, h2s_preview.hip) and by every unit that calls one (the host
+// units, h2s_testhooks.hip), so a signature or an
 // enum value that drifts apart is a compile error, not a misrouted launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,10 +26,12 @@ enum ProcessForm : unsigned { PF_VEC = 1, PF_OUT8 = 2, PF_C444 = 4 };
 hipError_t launch_process(const KParams& P, unsigned form, hipStream_t s);
 hipError_t launch_debug(const KParams& P, int stage, float* out, hipStream_t s);
 hipError_t launch_chroma_bicubic(const KParams& P, const float* wx7, const float* wy8, bool out8, hipStream_t s);
+hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
+
+// h2s_peak.hip
 hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& T, hipStream_t s);
 hipError_t launch_peak_curves(double2* fstat, int n, const PeakModel& M, PeakState* st, CurveConsts* out,
                               hipStream_t s);
-hipError_t build_lut8x(const float4* lut, int n, unsigned* out, hipStream_t s);
 
 // h2s_fast.hip
 bool fast_supported(int tonemap);

@@ -6,7 +6,7 @@
 // peak in the tile kernel's folded form (CurveConsts).
 //
 // One definition serves the host (the static curve of h2s_set_params) and the
-// device (k_peak_stats* + k_peak_finish in h2s_kernels.hip: h2s_process with
+// device (k_peak_stats* + k_peak_finish in h2s_peak.hip: h2s_process with
 // peak_detect queues the statistics, then the per-frame fold with the IIR and
 // curve records in its last block, then the conversion, on its stream with no
 // host round trip; k_peak_curves serves h2s_peak_feed), so the two cannot
@@ -54,7 +54,7 @@ struct PeakState {
 };
 
 // The buffers of a statistics launch (k_peak_stats* then k_peak_finish, in
-// h2s_kernels.hip).  The histograms and the counter are zero on entry and are
+// h2s_peak.hip).  The histograms and the counter are zero on entry and are
 // left zero (h2s_api_peak.hip frame_stats clears them once, at allocation).
 struct PeakTail {
   PeakModel M;
@@ -64,7 +64,6 @@ struct PeakTail {
   PeakState* st;       // null: the statistics only (h2s_peak_stats)
   CurveConsts* out;    // nframes curve records, or null
   int nframes;
-  int form;            // PQ statistics form: 0 = 32-pixel quad units (default), 1 = 8-pixel row chunks (test hook A/B)
 };
 
 __host__ __device__ inline double hd_pq_encode(double y) {

@@ -109,12 +109,6 @@ __device__ __forceinline__ void nt_st4(uint4 w, uint8_t* p) {
   __builtin_nontemporal_store(u4v{w.x, w.y, w.z, w.w}, reinterpret_cast<u4v*>(p));
 }
 
-
-__device__ __forceinline__ long long fxcd_remap(long long b, long long nb) {
-  const long long xcd = b & 7, idx = b >> 3, per = nb >> 3, rem = nb & 7;
-  return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
-
 // exact zimg st_2084_eotf x 2^log2_scale (S1: 10000/npl for PQ input; used
 // above the table's range and in its first segment)
 __device__ __forceinline__ float pq_exact_s(float e, float log2_scale) {
@@ -1381,7 +1375,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   const int t = threadIdx.x;
   const int lane = t & 63, w = t >> 6;
   const unsigned ntiles = F.nbx * F.nby * F.nframes;
-  unsigned tile = (unsigned)fxcd_remap(blockIdx.x, gridDim.x) * (unsigned)F.tpb;
+  unsigned tile = (unsigned)xcd_remap(blockIdx.x, gridDim.x) * (unsigned)F.tpb;
   const unsigned tend = tile + (unsigned)F.tpb < ntiles ? tile + (unsigned)F.tpb : ntiles;
 
   // ---- prologue: first tile + tables, all issued before any wait ----

@@ -54,7 +54,7 @@ OPT_FAST_PATH, OPT_TILES_PER_BLOCK, OPT_HOST_SERIAL, OPT_LP_EXACT = 1, 2, 3, 5
 OPT_RESERVED_4 = 4   # H2S_OPT_LP_EXACT's key in ABI 3.3: now INVALID_ARG
 # private test hook (include/h2s.h H2S_PRIVATE_TEST_HOOKS: not part of the ABI)
 OPT_TEST_FAIL_AFTER_LAUNCH = 0x7f000000 + 1
-OPT_TEST_PEAK_FORM = 0x7f000000 + 2
+OPT_RESERVED_PRIVATE_2 = 0x7f000000 + 2   # was OPT_TEST_PEAK_FORM: now INVALID_ARG
 OPT_TEST_PEAK_CHUNK = 0x7f000000 + 3
 OPT_TEST_PEAK_BLOCKS = 0x7f000000 + 4
 PATH_TILE, PATH_TILE_TAIL, PATH_GENERIC, PATH_TWO_PASS = 1, 2, 3, 4

@@ -24,8 +24,9 @@ ARCH = os.environ.get('H2S_OFFLOAD_ARCH', 'gfx950')
 SOURCES = ['h2s_kernels.hip', 'h2s_debug_lp_dv_semi.hip', 'h2s_debug_lp_dv.hip', 'h2s_fast_lp_dv_semi.hip',
            'h2s_fast_lp_dv.hip', 'h2s_fast_lp.hip', 'h2s_fast_lp_semi.hip', 'h2s_fast_lp_tl.hip', 'h2s_debug_semi.hip',
            'h2s_debug.hip', 'h2s_debug_lp_semi.hip', 'h2s_debug_lp.hip', 'h2s_fast_semi.hip', 'h2s_fast_tl.hip',
-           'h2s_fast_sub422.hip', 'h2s_fast.hip', 'h2s_fast_sub444.hip', 'h2s_api.hip', 'h2s_resolve.hip',
-           'h2s_api_peak.hip', 'h2s_api_preview.hip', 'h2s_api_dovi.hip', 'h2s_preview.hip', 'h2s_cube.cpp']
+           'h2s_fast_sub422.hip', 'h2s_fast.hip', 'h2s_fast_sub444.hip', 'h2s_peak.hip', 'h2s_api.hip',
+           'h2s_resolve.hip', 'h2s_api_peak.hip', 'h2s_api_preview.hip', 'h2s_api_dovi.hip', 'h2s_preview.hip',
+           'h2s_testhooks.hip', 'h2s_cube.cpp']
 HEADERS = ['h2s_device.h', 'h2s_tile.h', 'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_dovi.h', 'h2s_srcprev.h',
            'h2s_launch.h', 'h2s_host.h']
 
@@ -60,6 +61,8 @@ SOURCE_FLAGS = {
     # branch's exact path): no FMA contraction, so its float arithmetic rounds
     # where the oracle's does
     'h2s_kernels.hip': ['-ffp-contract=off'],
+    # the peak statistics' per-pixel sums (peak_px) round where they are written
+    'h2s_peak.hip': ['-ffp-contract=off'],
 }
 
 

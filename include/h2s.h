@@ -234,7 +234,8 @@ enum h2s_option {
   H2S_OPT_FAST_PATH = 1,       /* 1 (default): the tile kernel where it applies; 0: generic kernel only */
   H2S_OPT_TILES_PER_BLOCK = 2, /* tile kernel: 64x32 tiles one block walks (1..64, default 8)          */
   H2S_OPT_HOST_SERIAL = 3,     /* host frames: 1 = one H2D, kernel, D2H per call (no chunk pipeline)   */
-  /* 4: reserved (H2S_E_INVALID_ARG; was H2S_OPT_LP_EXACT in ABI 3.3)                                  */
+  /* 4: reserved (H2S_E_INVALID_ARG; was H2S_OPT_LP_EXACT in ABI 3.3), as is the private key           */
+  /* H2S_OPT_PRIVATE_BASE + 2 (was H2S_OPT_TEST_PEAK_FORM): neither is given a new meaning             */
   H2S_OPT_LP_EXACT = 5         /* 1: the libplacebo branch on its exact path only (see below)           */
 };
 /* H2S_OPT_LP_EXACT: the libplacebo branch's 8-bit rgba download rounds a
@@ -254,8 +255,7 @@ enum h2s_option {
 /* 1 = the next h2s_process call reports H2S_E_HIP right after queueing its
  * kernels (the error exits must still record the launch) */
 #define H2S_OPT_TEST_FAIL_AFTER_LAUNCH (H2S_OPT_PRIVATE_BASE + 1)
-/* peak statistics kernel form (A/B measurements): 0 = 32-pixel quad units (default), 1 = round 5's row chunks */
-#define H2S_OPT_TEST_PEAK_FORM (H2S_OPT_PRIVATE_BASE + 2)
+/* H2S_OPT_PRIVATE_BASE + 2: reserved (H2S_E_INVALID_ARG; was H2S_OPT_TEST_PEAK_FORM, the statistics kernels' A/B) */
 /* dynamic peak on the tile kernel: frames per pipelined chunk (0 = statistics for
  * the whole batch, then one conversion launch) */
 #define H2S_OPT_TEST_PEAK_CHUNK (H2S_OPT_PRIVATE_BASE + 3)

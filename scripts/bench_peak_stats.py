@@ -1,8 +1,9 @@
-"""A/B of the peak-statistics kernel forms (H2S_OPT_TEST_PEAK_FORM) and the
-dynamic-peak overhead of C3 (16 4K frames per call): per form, the time of
+"""The dynamic-peak overhead of C3 (16 4K frames per call): the time of
 h2s_process with peak_detect against the static call, HIP events on the call's
-stream, median of runs.  Run under rocprofv3 --kernel-trace for per-kernel
-durations.  GPU box.  Usage: python scripts/bench_peak_stats.py"""
+stream, median of runs, and the same at other block counts per frame.  Run
+under rocprofv3 --kernel-trace for per-kernel durations.  (The statistics
+kernels' form A/B this script also ran was decided in round 6; its code is
+profiles/peak_unit/ab_patches/.)  GPU box.  Usage: python scripts/bench_peak_stats.py"""
 import json
 import os
 import sys
@@ -41,16 +42,12 @@ for dyn in (False, True):
     p = hdr2sdr.TonemapParams(tonemapper='bt.2390', gamma=1.0, bits_out=10, peak_detect=dyn, maxcll=4000.0)
     tm = hdr2sdr.Tonemapper(0, p, lat)
     out = tm(src)            # allocates a device batch of the right shape
-    forms = (0, 1, 2) if dyn else (0,)   # 0: quad units (default), 1: round-5 row chunks, 2: quad, 4 in flight
-    for form in forms:
-        tm.set_option(_abi.OPT_TEST_PEAK_FORM, form)
-        res[f'{"dyn" if dyn else "static"}_form{form}_ms'] = round(timed(tm, out), 4)
-        print(json.dumps(res), flush=True)
-    if dyn:   # partial records (blocks) per frame, quad form
-        tm.set_option(_abi.OPT_TEST_PEAK_FORM, 0)
+    res[f'{"dyn" if dyn else "static"}_ms'] = round(timed(tm, out), 4)
+    print(json.dumps(res), flush=True)
+    if dyn:   # partial records (blocks) per frame
         for nb in (128, 256, 64):
             tm.set_option(_abi.OPT_TEST_PEAK_BLOCKS, nb)
-            res[f'dyn_form0_blocks{nb}_ms'] = round(timed(tm, out), 4)
+            res[f'dyn_blocks{nb}_ms'] = round(timed(tm, out), 4)
             print(json.dumps(res), flush=True)
     tm.close()
 # the statistics alone (h2s_peak_stats: the finish kernel without IIR / curve
@@ -62,6 +59,5 @@ for pct in (float('nan'), 100.0):
     for _ in range(20):
         tm.peak_stats(src)
     tm.close()
-res['dyn_minus_static_form0'] = round(res['dyn_form0_ms'] - res['static_form0_ms'], 4)
-res['dyn_minus_static_form1'] = round(res['dyn_form1_ms'] - res['static_form0_ms'], 4)  # round 5's row form
+res['dyn_minus_static'] = round(res['dyn_ms'] - res['static_ms'], 4)
 print(json.dumps(res))

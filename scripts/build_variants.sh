@@ -31,8 +31,8 @@ for spec in "$@"; do
         h2s_fast_lp.hip) rebuild=1;;
         # DBG=1: the debug instances (h2s_debug_float) get the flags too
         h2s_debug.hip|h2s_debug_lp.hip) rebuild=${DBG:-0};;
-        # KERN=1: h2s_kernels.hip (generic kernel, peak statistics) gets the flags too
-        h2s_kernels.hip) rebuild=${KERN:-0};;
+        # KERN=1: h2s_kernels.hip (generic kernel) and h2s_peak.hip (peak statistics) get the flags too
+        h2s_kernels.hip|h2s_peak.hip) rebuild=${KERN:-0};;
       esac
       if [ "$rebuild" = 1 ]; then
         o="$V/${s%.*}_$name.o"

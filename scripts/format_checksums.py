@@ -39,6 +39,31 @@ matrices x both RGB models at 128x64 -> 51x25 (odd width: the half pair),
 identity and 2x up for bt2020nc / trunc16.
 
   [H2S_LIB=...] python scripts/format_checksums.py --preview OUT.json
+
+--peak OUT.json instead hashes the dynamic peak's own results, one JSON line:
+the raw bytes of h2s_peak_stats's per-frame (measurement, average) of a
+3-frame batch ("stats/...") and of peak_state() after reset_peak and one
+3-frame process ("state/...").  PQ 10-bit and HLG 12-bit, planar and
+semi-planar input, pd_percentile default (histograms) and 100 (none), at one
+width per statistics form and heights chosen from the launch geometry: the
+default PEAK_BLOCKS = 128 blocks of 256 threads give a thread stride of 32768
+units.
+  208 wide, PQ: the quad form, 13 units per row pair, 2 in flight.  22688 rows
+    are 147472 units, 4.5 strides: every thread runs two in-flight groups (the
+    loop's own step is taken), and the threads of the first half stride then
+    one unit in the remainder loop, the rest none.
+  208 wide, HLG (never quad) and 200 wide (8 | W, not 16): the 8-pixel
+    row-chunk form, 26 / 25 chunks per row, 4 in flight.  11142 rows are 289692
+    / 278550 chunks, 8.84 / 8.5 strides: every thread runs two groups of four,
+    then the threads below 0.84 / 0.5 stride one chunk in the remainder loop.
+  204 wide: the 2-byte row form, one row per block and step; 258 rows give
+    blocks 0 and 1 a third row.
+  64 rows at every width: 416 / 1664 / 1600 units, under one stride, so only
+    the remainder loop runs (and half the row form's blocks idle).
+A Dolby Vision record set (three luma maps, tests/dovi_ref.py) goes through
+the row form at 208x64, planar PQ 10-bit.
+
+  [H2S_LIB=...] python scripts/format_checksums.py --peak OUT.json
 """
 import ctypes
 import dataclasses
@@ -182,7 +207,66 @@ def preview(path):
     return 0
 
 
+PEAK_SOURCES = {'pq10': dict(bits_in=10), 'hlg12': dict(transfer='arib-std-b67', bits_in=12, bits_out=12)}
+# (width, source) -> heights: both loops of the form, then the remainder loop alone (the docstring)
+PEAK_SIZES = {(208, 'pq10'): (22688, 64), (208, 'hlg12'): (11142, 64), (200, 'pq10'): (11142, 64),
+              (200, 'hlg12'): (11142, 64), (204, 'pq10'): (258, 64), (204, 'hlg12'): (258, 64)}
+
+
+def peak(path):
+    import struct
+
+    import dovi_ref as DR
+    import torch
+
+    import hdr2sdr
+    from hdr2sdr.frames import FrameBatch
+    from hdr2sdr.synth import synth_frames
+
+    lattice = hdr2sdr.generate_lattice(LUT_N)
+    res = {}
+    tm = hdr2sdr.Tonemapper(0)
+
+    def case(key, params, src):
+        fmax, favg = tm.peak_stats(src)
+        res[f'stats/{key}'] = _sha(np.stack([fmax, favg]))
+        dst = FrameBatch.empty_torch(NF, src.width, src.height, params.bits_out, 'cuda', 'planar')
+        tm.reset_peak()
+        tm.process(src, dst)
+        torch.cuda.synchronize()
+        st = tm.peak_state()
+        res[f'state/{key}'] = hashlib.sha256(struct.pack('<dddq', st['max_pq'], st['avg_pq'], st['peak'],
+                                                         st['frames'])).hexdigest()
+
+    for (W, name), heights in sorted(PEAK_SIZES.items()):
+        for H in heights:
+            planar = synth_frames('smooth', NF, W, H, PEAK_SOURCES[name]['bits_in'], device='cpu', seed=SEED).to_numpy()
+            for pct in (None, 100.0):
+                kw = dict(PEAK_SOURCES[name], **({} if pct is None else dict(pd_percentile=pct)))
+                params = hdr2sdr.TonemapParams(tonemapper='bt.2390', peak_detect=True, maxcll=4000.0, **kw)
+                tm.set_params(params)
+                tm.set_lut(lattice)
+                for layout in ('planar', 'semi'):
+                    case(f'{name}/{W}x{H}/{layout}/pct-{"default" if pct is None else pct}', params,
+                         planar.to_layout(layout).to_torch('cuda'))
+    W, H = 208, 64
+    src, recs, _ = DR.luma_map_pair(W, H, 10, NF)
+    for pct in (None, 100.0):
+        params = hdr2sdr.TonemapParams(tonemapper='bt.2390', peak_detect=True, maxcll=4000.0,
+                                       **({} if pct is None else dict(pd_percentile=pct)))
+        tm.set_params(params)
+        tm.set_lut(lattice)
+        tm.set_dovi(recs)
+        case(f'dovi-maps/{W}x{H}/planar/pct-{"default" if pct is None else pct}', params, src.to_torch('cuda'))
+        tm.set_dovi(None)
+    tm.close()
+    _write(res, path)
+    return 0
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == '--peak':
+        return peak(sys.argv[2])
     if len(sys.argv) == 3 and sys.argv[1] == '--debug-planes':
         return debug_planes(sys.argv[2])
     if len(sys.argv) == 3 and sys.argv[1] == '--preview':

@@ -106,6 +106,22 @@ def test_null_handling_without_device():
         _abi.raise_for(_abi.H2S_E_HIP, 'x')
 
 
+def test_retired_peak_form_key_is_reserved():
+    """The statistics kernels' A/B option (H2S_OPT_TEST_PEAK_FORM, private key
+    2) is retired.  This test pins the header and the binding only: the header
+    defines no such name and documents the key as reserved, and the binding has
+    no constant for setting it.  No context can be made without a device, so
+    the call below gets the NULL-context answer, which every key gets; that the
+    library answers this key on a context with H2S_E_INVALID_ARG and "reserved"
+    is tests/test_gpu_parity.py::test_retired_peak_form_key_is_reserved."""
+    src = open(HEADER).read()
+    assert not re.search(r'#define\s+H2S_OPT_TEST_PEAK_FORM\b', src)
+    assert re.search(r'H2S_OPT_PRIVATE_BASE \+ 2: reserved \(H2S_E_INVALID_ARG', src)
+    assert not hasattr(_abi, 'OPT_TEST_PEAK_FORM')
+    assert _abi.OPT_RESERVED_PRIVATE_2 == 0x7f000002
+    assert _abi.lib().h2s_set_option(None, _abi.OPT_RESERVED_PRIVATE_2, 1) == _abi.H2S_E_INVALID_ARG
+
+
 def test_product_path_fails_loudly_without_the_library(tmp_path):
     """No CPU fallback: with libh2s missing, the first pixel call raises
     ImportError (the package itself still imports)."""

@@ -784,3 +784,13 @@ def test_option_4_is_reserved(tm):
     with pytest.raises(ValueError, match='reserved'):
         tm.set_option(_abi.OPT_RESERVED_4, 1)
     tm.set_option(_abi.OPT_LP_EXACT, 0)
+
+
+def test_retired_peak_form_key_is_reserved(tm):
+    """Private key 2 was H2S_OPT_TEST_PEAK_FORM (the statistics kernels' A/B);
+    it is reserved like key 4, whatever the value, and its neighbours stand."""
+    from hdr2sdr import _abi
+    for value in (0, 1, 2):
+        with pytest.raises(ValueError, match='reserved'):
+            tm.set_option(_abi.OPT_RESERVED_PRIVATE_2, value)
+    tm.set_option(_abi.OPT_TEST_PEAK_CHUNK, 0)

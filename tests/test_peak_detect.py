@@ -209,7 +209,7 @@ def _saturated_frames(W, H):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('pct', [float('nan'), 90.0, 100.0])   # nan: vf_libplacebo's 99.995
-@pytest.mark.parametrize('W,H', [(256, 128), (200, 96)])       # quad form; row / generic form
+@pytest.mark.parametrize('W,H', [(256, 128), (200, 96), (204, 96)])   # quad form; 8-pixel row chunks; 2-byte row form
 def test_gpu_peak_stats_equal_the_oracle(W, H, pct):
     """h2s_peak_stats (the per-frame percentile measurement and mean) against
     the oracle's, on the sequence and on frames with saturated pixels, whose
