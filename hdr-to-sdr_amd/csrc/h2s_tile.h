@@ -24,6 +24,14 @@
 // chroma is reduced per quad with DPP quad permutes and all outputs leave
 // through LDS as 16-byte coalesced stores.  Measured balance (DESIGN.md
 // §4.1): VALU ~70 % busy, LDS ~47 %, vector-memory return ~35 %.
+// Tile I/O ("The tile I/O"): luma lies in LDS as the 16-bit
+// codes that were loaded (luma_at): a step converts its sample and writes
+// the output code over it, and the store phase moves 16 bytes unchanged.
+// Every thread issues the same loads and the same two 16-byte stores per
+// tile under no branch (tile_load, tile_store: what a thread does not need
+// goes to an offset the buffer resource drops), and a tile is committed
+// behind the previous tile's stores, so the compiler's counted waits for
+// the loads never wait for a store.  Two barriers per tile.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -857,8 +865,9 @@ constexpr int CBW = 32, CBH = 16;  // chroma tile
 #ifndef H2S_YST
 #define H2S_YST 72
 #endif
-// LDS row stride (floats) of the staged luma tile and of the horizontally
-// upsampled chroma rows.  72 on the CPU chain's instances: a step's 8 rows x 8
+// LDS row stride (floats) of the horizontally upsampled chroma rows (and, until
+// the luma tile became 16-bit codes at its own stride, luma_at, of the staged
+// luma floats: the measurements below are of both).  72 on the CPU chain's instances: a step's 8 rows x 8
 // columns then start 8 banks apart and cover all 64 banks (68 overlapped
 // 2-way: 34 % -> 20 % of LDS-active cycles in bank conflicts, time unchanged;
 // profiles/r04/ablations/lds_stride.txt).  68 on the libplacebo instances,
@@ -922,7 +931,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const uint8_t* base
 template <bool SEMI, int SUB = 0>
 struct TileRegs {
   uint4 ya, ua;     // luma chunk; chroma chunk of plane pc (threads tc < 72)
-  std::conditional_t<SEMI, unsigned, uint16_t> uh;   // the chroma chunk's right-halo sample (SEMI: or pair)
+  std::conditional_t<SEMI, unsigned, uint16_t> uh;   // the chroma chunk's right-halo sample (SEMI: or pair; planar input: the word that holds it, halo_half)
 };
 template <bool SEMI>
 struct TileRegs<SEMI, 2> {
@@ -1060,13 +1069,19 @@ __device__ __forceinline__ TileRegs<SEMI, SUB> tile_load(const FastParams& F, co
     r.uh = __builtin_amdgcn_raw_buffer_load_b16(ic, vh, sc, 0);
     return r;
   } else {
-  if (SEMI && F.in_semi) {   // block-uniform
+  // One chunk load and one halo load for both layouts of a SEMI instance (the
+  // layouts differ in plane, offsets and the halo's width, not in the
+  // instructions: two arms that each held their loads would leave the
+  // compiler a path with neither and one with both, and its waits for the
+  // second arm's registers would drain the previous tile's stores)
+  const bool pair = SEMI && F.in_semi;   // block-uniform
+  int pc, vc, vh, sc;
+  if (pair) {
     // the interleaved plane: 18 rows x 8 chunks of four (Cb, Cr) pairs on
     // threads 0..143, each with the pair right of its chunk (4 bytes), so
     // every line of the plane is read once
-    const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1] + g.f * F.in_fp[1], F.in_bytes[1]);
+    pc = 0;
     const int ls = (int)F.in_ls[1];
-    int vc, vh, sc;
     if (g.cy0 >= 1 && g.cy0 + CBH + 1 <= F.ch && g.cx0 + CBW + 1 <= F.cw) {   // block-uniform
       vc = L.u, vh = L.u + 16, sc = (g.cy0 - 1) * ls + 4 * g.cx0;
     } else {
@@ -1077,44 +1092,71 @@ __device__ __forceinline__ TileRegs<SEMI, SUB> tile_load(const FastParams& F, co
       sc = 0;
     }
     if (t >= 144) vc = vh = 0x7FFFFFF0;
-    r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ic, vc, sc, NT));
-    r.uh = __builtin_amdgcn_raw_buffer_load_b32(ic, vh, sc, 0);
-    return r;
-  }
-  const int pc = __builtin_amdgcn_readfirstlane(t >> 7), tc = t & 127;
-  const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1 + pc] + g.f * F.in_fp[1 + pc], F.in_bytes[1 + pc]);
-  const int ls = (int)F.in_ls[1 + pc];
-  int vc, vh, sc;
-  if (g.cy0 >= 1 && g.cy0 + CBH + 1 <= F.ch && g.cx0 + CBW + 1 <= F.cw) {   // block-uniform
-    vc = L.u, vh = L.u + 16, sc = (g.cy0 - 1) * ls + 2 * g.cx0;
   } else {
-    const int clr = tc >> 2, ccx = tc & 3;
-    const int row = chroma_edge_at(g.cy0 - 1 + clr, F.ch, F.chroma_edge);
-    vc = row * ls + 2 * (g.cx0 + 8 * ccx);
-    vh = row * ls + 2 * chroma_edge_at(g.cx0 + 8 * ccx + 8, F.cw, F.chroma_edge);
-    sc = 0;
+    pc = __builtin_amdgcn_readfirstlane(t >> 7);
+    const int tc = t & 127;
+    const int ls = (int)F.in_ls[1 + pc];
+    if (g.cy0 >= 1 && g.cy0 + CBH + 1 <= F.ch && g.cx0 + CBW + 1 <= F.cw) {   // block-uniform
+      vc = L.u, vh = L.u + 16, sc = (g.cy0 - 1) * ls + 2 * g.cx0;
+    } else {
+      const int clr = tc >> 2, ccx = tc & 3;
+      const int row = chroma_edge_at(g.cy0 - 1 + clr, F.ch, F.chroma_edge);
+      vc = row * ls + 2 * (g.cx0 + 8 * ccx);
+      vh = row * ls + 2 * chroma_edge_at(g.cx0 + 8 * ccx + 8, F.cw, F.chroma_edge);
+      sc = 0;
+    }
+    if (tc >= 72) vc = vh = 0x7FFFFFF0;
   }
-  if (tc >= 72) vc = vh = 0x7FFFFFF0;
+  const __amdgpu_buffer_rsrc_t ic = plane_rsrc(F.in[1 + pc] + g.f * F.in_fp[1 + pc], F.in_bytes[1 + pc]);
+  sc = __builtin_amdgcn_readfirstlane(sc);   // (block-uniform; said so, or the merged origin costs a lane loop per load)
   r.ua = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ic, vc, sc, NT));
-  r.uh = __builtin_amdgcn_raw_buffer_load_b16(ic, vh, sc, 0);
+  if constexpr (SEMI) {
+    // the halo as the aligned word that holds it (rows and scalar origins are
+    // 4-byte aligned, so the word lies inside the plane): the pair itself,
+    // or the word with the planar sample, whose half halo_half takes at the
+    // commit (not here: that would wait for the load)
+    r.uh = __builtin_amdgcn_raw_buffer_load_b32(ic, vh & ~2, sc, 0);
+  } else {
+    r.uh = __builtin_amdgcn_raw_buffer_load_b16(ic, vh, sc, 0);
+  }
   return r;
   }
 }
 
+// a SEMI instance's planar 4:2:0 halo sample from the word tile_load read for
+// tile g: the low half, or on a border tile the half of the clamped column
+__device__ __forceinline__ unsigned halo_half(const FastParams& F, const TileGeo& g, int t, unsigned hw) {
+  int hs = 0;
+  if (!(g.cy0 >= 1 && g.cy0 + CBH + 1 <= F.ch && g.cx0 + CBW + 1 <= F.cw))   // block-uniform, as tile_load
+    hs = (chroma_edge_at(g.cx0 + 8 * (t & 3) + 8, F.cw, F.chroma_edge) & 1) << 4;
+  return (hw >> hs) & 0xffffu;
+}
+
 // staging and store helpers of k_tile
-// 8 luma samples -> Y*ys + y_off floats at (row, 8 col8)
-// returns the largest staged value
-template <int YST>
-__device__ __forceinline__ float stage_luma(float* yin, uint4 a, int row, int col8, float ysc, float yoff) {
-  float v[8];
-  unpack8(a, v);
-  float* d = yin + row * YST + 8 * col8;
-  const float4 lo = make_float4(fmaf(v[0], ysc, yoff), fmaf(v[1], ysc, yoff), fmaf(v[2], ysc, yoff), fmaf(v[3], ysc, yoff));
-  const float4 hi = make_float4(fmaf(v[4], ysc, yoff), fmaf(v[5], ysc, yoff), fmaf(v[6], ysc, yoff), fmaf(v[7], ysc, yoff));
-  *reinterpret_cast<float4*>(d) = lo;
-  *reinterpret_cast<float4*>(d + 4) = hi;
-  return __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(lo.x, lo.y), __builtin_fmaxf(lo.z, lo.w)),
-                         __builtin_fmaxf(__builtin_fmaxf(hi.x, hi.y), __builtin_fmaxf(hi.z, hi.w)));
+// The luma tile in LDS: the 16-bit codes as loaded (after a semi-planar or
+// truncating input's shift and mask), pixel (x, y) of the 64 x 32 tile at
+// byte luma_at(x, y).  A step converts its sample (S0) and writes the output
+// code over it (S7); the store phase moves a chunk's 16 bytes as they are.
+// Row stride 144 bytes: the 8 rows of a step's 8 x 8 block start 36 dwords
+// apart, i.e. on banks 0, 4, .., 28 of the 32 that 16-bit reads and every
+// write use, and a row's 8 samples take 4 dwords (two lanes per dword, one
+// address), so a step's 64 reads and 64 writes have no bank conflict
+constexpr int YROW = 144;
+constexpr int luma_at(int x, int y) { return y * YROW + 2 * x; }
+static_assert(YROW % 16 == 0 && luma_at(8, 0) == 16, "a chunk of 8 samples is one aligned 16-byte slot");
+static_assert(luma_at(0, 1) >= luma_at(TBW - 1, 0) + 2, "the rows' slots are disjoint");
+static_assert((luma_at(0, 1) / 4) % 32 == 4 && luma_at(7, 0) / 4 == 3, "a step's 8 rows x 4 dwords cover the 32 banks once");
+constexpr int YIN_BYTES = luma_at(0, TBH);
+typedef unsigned short us2v __attribute__((ext_vector_type(2)));
+// commit the thread's chunk (row, 8 col8); returns its largest code staged
+// as the step stages it (fmaf is monotonic in the code: ysc > 0), for the
+// tile's branch-free-body flag
+__device__ __forceinline__ float stage_luma(unsigned char* yin, uint4 a, int row, int col8, float ysc, float yoff) {
+  *reinterpret_cast<uint4*>(yin + luma_at(8 * col8, row)) = a;
+  const us2v m = __builtin_elementwise_max(
+      __builtin_elementwise_max(__builtin_bit_cast(us2v, a.x), __builtin_bit_cast(us2v, a.y)),
+      __builtin_elementwise_max(__builtin_bit_cast(us2v, a.z), __builtin_bit_cast(us2v, a.w)));
+  return fmaf((float)(m.x > m.y ? m.x : m.y), ysc, yoff);
 }
 // horizontal pass (left siting, x2 scale) on centred codes c = code - mid:
 // h[2k] = 2 c[k], h[2k+1] = c[k] + c[k+1]; exact in float.  tt: chunk index
@@ -1203,24 +1245,40 @@ __device__ __forceinline__ float stage_chroma444(float* plane_u, float* plane_v,
   pack(b, plane_v, m);
   return m;
 }
-// luma codes of tile row r, chunk c (8 pixels), packed for one 16-byte (u16)
-// / 8-byte (u8: .xy) store
-template <int YST>
-__device__ __forceinline__ u4v read_luma(const FastParams& F, const float* yin, int r, int c) {
-  const unsigned* src = reinterpret_cast<const unsigned*>(yin) + r * YST + 8 * c;
-  const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 4);
+// luma codes of tile row r, chunk c (8 pixels) for the store: the 16 bytes as
+// they lie in LDS, or (8-bit output) their low bytes in .xy by two permutes
+__device__ __forceinline__ u4v read_luma(const FastParams& F, const unsigned char* yin, int r, int c) {
+  const uint4 a = *reinterpret_cast<const uint4*>(yin + luma_at(8 * c, r));
   if (F.out8)
-    return u4v{a.x | (a.y << 8) | (a.z << 16) | (a.w << 24), b.x | (b.y << 8) | (b.z << 16) | (b.w << 24), 0u, 0u};
-  return u4v{a.x | (a.y << 16), a.z | (a.w << 16), b.x | (b.y << 16), b.z | (b.w << 16)};
+    return u4v{__builtin_amdgcn_perm(a.y, a.x, 0x06040200u), __builtin_amdgcn_perm(a.w, a.z, 0x06040200u), 0u, 0u};
+  return u4v{a.x, a.y, a.z, a.w};
 }
-__device__ __forceinline__ void put_luma(const FastParams& F, const TileGeo& g, u4v v, int r, int vo, int so) {
-  if (g.py0 + r >= F.H) return;
+// Store rule (the loads' rule, tile_load): every thread issues exactly one
+// luma and one chroma store per tile, the same 16-byte instruction on every
+// path and under no branch, so the compiler counts them and its vmcnt waits
+// for the next tile's loads leave them outstanding (k_tile's commit).  A
+// branch around a store, even a block-uniform one between an 8-byte and a
+// 16-byte arm, leaves a path without it in the compiler's count.  A thread
+// with nothing to store (a row past the frame, no chroma role, the BICUBIC
+// scratch path) stores at ST_DROP, an offset at or past every plane extent
+// (those are clamped to 2^31 - 1, the offset is unsigned and the scalar
+// origin takes no part in the range check): the hardware drops it.
+// 8-bit output (v.xy = the thread's 8 bytes): threads t and t ^ 1 hold
+// neighbouring chunks of one row, so the even one stores both (the odd
+// thread's words by a DPP quad permute) and the odd one drops its store
+constexpr int ST_DROP = (int)0x80000000u;
+__device__ __forceinline__ void tile_store(const FastParams& F, u4v v, __amdgpu_buffer_rsrc_t rs, int vo, int so, int t) {
+  if (F.out8) {   // block-uniform
+    v.z = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.x, 0xB1, 0xF, 0xF, false);
+    v.w = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v.y, 0xB1, 0xF, 0xF, false);
+    if (t & 1) vo = ST_DROP;
+  }
+  __builtin_amdgcn_raw_buffer_store_b128(v, rs, vo, so, NTS);
+}
+__device__ __forceinline__ void put_luma(const FastParams& F, const TileGeo& g, u4v v, int r, int vo, int t) {
+  if (g.py0 + r >= F.H) vo = ST_DROP;
   const __amdgpu_buffer_rsrc_t oy_ = plane_rsrc(F.out[0] + g.f * F.out_fp[0], F.out_bytes[0]);
-  so += g.py0 * (int)F.out_ls[0];
-  if (F.out8)
-    __builtin_amdgcn_raw_buffer_store_b64(u2v{v.x, v.y}, oy_, vo, so + g.px0, NTS);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, oy_, vo, so + 2 * g.px0, NTS);
+  tile_store(F, v, oy_, vo, g.py0 * (int)F.out_ls[0] + (F.out8 ? g.px0 : 2 * g.px0), t);
 }
 // chroma plane pl, row r, chunk c (8 samples): ((c0 + c1) + (c2 + c3)) + bias,
 // quantised once per sample, packed as read_luma
@@ -1248,14 +1306,12 @@ __device__ __forceinline__ u4v read_chroma(const FastParams& F, const float* csu
                code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24), 0u, 0u};
   return u4v{code[0] | (code[1] << 16), code[2] | (code[3] << 16), code[4] | (code[5] << 16), code[6] | (code[7] << 16)};
 }
-__device__ __forceinline__ void put_chroma(const FastParams& F, const TileGeo& g, u4v v, int pl, int r, int vo) {
-  if (g.cy0 + r >= F.ch) return;
+// (vo: the lane's offset, or ST_DROP; semi: the interleaved plane, pl = 0, of
+// a semi-planar output, two codes per chroma column.  One store for both
+// layouts: see the store rule)
+__device__ __forceinline__ void put_chroma(const FastParams& F, const TileGeo& g, u4v v, int pl, bool semi, int vo, int t) {
   const __amdgpu_buffer_rsrc_t oc_ = plane_rsrc(F.out[1 + pl] + g.f * F.out_fp[1 + pl], F.out_bytes[1 + pl]);
-  const int so = g.cy0 * (int)F.out_ls[1 + pl];
-  if (F.out8)
-    __builtin_amdgcn_raw_buffer_store_b64(u2v{v.x, v.y}, oc_, vo, so + g.cx0, NTS);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, oc_, vo, so + 2 * g.cx0, NTS);
+  tile_store(F, v, oc_, vo, g.cy0 * (int)F.out_ls[1 + pl] + ((F.out8 ? g.cx0 : 2 * g.cx0) << (semi ? 1 : 0)), t);
 }
 
 // semi-planar output: row r, chunk c (four (Cb, Cr) pairs) of the tile's 16 x
@@ -1286,21 +1342,13 @@ __device__ __forceinline__ u4v read_chroma_semi(const FastParams& F, const float
   return u4v{(code[0] | (code[1] << 16)) << F.out_sh, (code[2] | (code[3] << 16)) << F.out_sh,
              (code[4] | (code[5] << 16)) << F.out_sh, (code[6] | (code[7] << 16)) << F.out_sh};
 }
-__device__ __forceinline__ void put_chroma_semi(const FastParams& F, const TileGeo& g, u4v v, int r, int vo) {
-  if (g.cy0 + r >= F.ch) return;
-  const __amdgpu_buffer_rsrc_t oc_ = plane_rsrc(F.out[1] + g.f * F.out_fp[1], F.out_bytes[1]);
-  const int so = g.cy0 * (int)F.out_ls[1];
-  if (F.out8)
-    __builtin_amdgcn_raw_buffer_store_b64(u2v{v.x, v.y}, oc_, vo, so + 2 * g.cx0, NTS);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, oc_, vo, so + 4 * g.cx0, NTS);
-}
-
 // Each block walks F.tpb consecutive tiles (XCD-remapped, so neighbouring
 // tiles and their lattice cells share one XCD's L2).  The loads of tile i+1
 // are issued before tile i is computed, so after the first tile the block no
-// longer waits on HBM latency.  Per tile: commit registers -> LDS, prefetch,
-// barrier, 8 compute steps, barrier, store, barrier.  (A fifth wave doing all
+// longer waits on HBM latency.  Per tile: prefetch, barrier, 8 compute steps,
+// barrier, store, commit the next tile's registers -> LDS (the first tile's
+// commit precedes the loop; no barrier between store and commit, see the
+// loop's end).  (A fifth wave doing all
 // of the frame I/O, so that the compute waves' gathers never wait behind the
 // prefetch in the shared vector-memory counter, measured 1.5x slower: its
 // serial store + commit phase idles the four compute waves;
@@ -1359,7 +1407,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   constexpr bool S420 = SUB == 0 || SUB == 3;   // the input is 4:2:0 (4:2:0 loads and staging)
   constexpr int YST = row_stride<LP>(), HST = YST;
   static_assert(TBH * C422_ST <= (CBH + 2) * HST && TBH * C444_ST <= 2 * (CBH + 2) * HST, "hrow holds the SUB windows");
-  __shared__ float yin[TBH * YST];             // luma samples x ys; output codes overwrite them in place
+  __shared__ __attribute__((aligned(16))) unsigned char yin[YIN_BYTES];   // luma codes (luma_at); output codes overwrite them in place
   __shared__ float hrow[2][(CBH + 2) * HST];   // chroma rows (halo incl.) upsampled x2 horizontally
   __shared__ float csum[2][CBH * CBW];         // per chroma sample: sum of its 2x2 pixel contributions
   __shared__ float4 pq_lds[PQ_NSEG + 1];       // [0] = zero segment (pq_z): PQ EOTF, or HLG inverse OETF (!LP)
@@ -1427,7 +1475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   // position lane&3 in the quad) ----
   const int qx = (lane >> 2) & 3, qy = lane >> 4, pxl = lane & 1, pyl = (lane >> 1) & 1;
   const int xl = 16 * w + 2 * qx + pxl, yl = 2 * qy + pyl;           // step (0,0) pixel
-  const float* ybase = yin + yl * YST + xl;
+  uint16_t* ybase = reinterpret_cast<uint16_t*>(yin + luma_at(xl, yl));   // this lane's sample of step (0, 0)
   // vertical pass (centre siting): 3 x row cy + row cy-1 (top) / cy+1 (bottom)
   const float* h0 = hrow[0] + (qy + 1) * HST + xl;
   const float* h1 = hrow[1] + (qy + 1) * HST + xl;
@@ -1476,6 +1524,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
   // are one straight-line block the scheduler can interleave
   auto steps = [&](const TileGeo& g, auto fast) {
     constexpr bool FB = decltype(fast)::value;
+    constexpr int YR2 = YROW / 2;   // the luma tile's row stride in samples
     if constexpr (FB) {
       H2S_MARK("body: fast");
     } else {
@@ -1500,6 +1549,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       cv.sp_srcmax = in_vgpr(cv.sp_srcmax), cv.sp_umax = in_vgpr(cv.sp_umax);
     }
     const __amdgpu_buffer_rsrc_t lut = __builtin_amdgcn_make_buffer_rsrc((void*)F.lut_yuv, (short)0, F.lut_bytes, 0x00020000);
+    // A step pair whose 8 rows lie past the frame's last row computes what is
+    // never stored (the bottom tile row of a 2160-row frame: steps 4-7), so it
+    // is skipped: block-uniform, product instances, not the BICUBIC scratch
+    // path.  Only this exact-capable body tests for it (k_tile sends such
+    // tiles here), so the fast body stays one straight-line block
+    const int live = !FB && DBG == 0 && !F.chr444 ? F.H - g.py0 : TBH;   // the tile's rows inside the frame
     // the 2x2 chroma sums of step s (or, BICUBIC, the pixel's Cb, Cr into the
     // frame's 4:4:4 scratch, which k_chroma_bicubic decimates; the scratch
     // has whole tiles of rows: rows past F.H are written, never read)
@@ -1528,11 +1583,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 #pragma unroll
         for (int s = 0; s <= 8; s++) {
           unsigned vn = 0;
-          if (s < 8) {
-            const int oy = 8 * (s >> 1) * YST + 8 * (s & 1);
+          if (s < 8 && (FB || 8 * (s >> 1) < live)) {
+            const int oy = 8 * (s >> 1) * YR2 + 8 * (s & 1);
             const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
             H2S_MARK("S0 step: staged Y, vertical chroma");
-            const float ybs = ybase[oy];
+            const float ybs = fmaf((float)ybase[oy], ysc, yoff);
             // x8 upsampled, centred, exact (SUB 3: 4 h[cy], or 2 (h[cy] + h[cy+1]))
             const float U = SUB == 3 ? 2.0f * (h0[oh] + h0[oh + hb]) : fmaf(3.0f, h0[oh], h0[oh + hb]);
             const float V = SUB == 3 ? 2.0f * (h1[oh] + h1[oh + hb]) : fmaf(3.0f, h1[oh], h1[oh + hb]);
@@ -1542,14 +1597,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
             H2S_MARK("S3 encode");
             vn = lp_table_read(F, K, lut8v, spread_lds, r, gg, bl, qo[s & 3]);
           }
-          if (s > 0) {
+          if (s > 0 && (FB || 8 * ((s - 1) >> 1) < live)) {
             const int sp = s - 1;
             const float R8 = (float)(vp & 255u), G8 = (float)((vp >> 8) & 255u), B8 = (float)((vp >> 16) & 255u);
             H2S_MARK("S5 Y'CbCr");
             const f3 o = lp_ycbcr(F, K, R8, G8, B8);
             H2S_MARK("S7 eq");
             // luma code (eq applied, shifted) replaces the luma sample this lane read
-            reinterpret_cast<unsigned*>(yin)[yl * YST + xl + 8 * (sp >> 1) * YST + 8 * (sp & 1)] = eq_lds[(int)o.x];
+            ybase[8 * (sp >> 1) * YR2 + 8 * (sp & 1)] = eq_lds[(int)o.x];
             chroma_out(sp, o.y, o.z);
           }
           vp = vn;
@@ -1560,10 +1615,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     }
 #pragma unroll
     for (int s = 0; s < 8; s++) {
-      const int oy = 8 * (s >> 1) * YST + 8 * (s & 1);   // compile-time LDS offsets
+      if (!FB && (s & 1) == 0 && 8 * (s >> 1) >= live) break;
+      const int oy = 8 * (s >> 1) * YR2 + 8 * (s & 1);   // compile-time LDS offsets
       const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
       H2S_MARK("S0 step: staged Y, vertical chroma");
-      const float ybs = ybase[oy];
+      const float ybs = fmaf((float)ybase[oy], ysc, yoff);   // (the staged luma: Y*ys + y_off, +1 on PQ)
       float U, V;
       if constexpr (SUB == 1) {   // 4 h at the pixel's row: 8 c[k], or 4 (c[k] + c[k+1])
         const int oc = 8 * (s >> 1) * C422_ST + 4 * (s & 1);
@@ -1582,7 +1638,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
                                : -1;
       float oyv, ozv;
       // luma code (eq applied, shifted) replaces the luma sample this lane read
-      reinterpret_cast<unsigned*>(yin)[yl * YST + xl + oy] = px_chain<TRC, TM, DESAT, LP, DBG, FB>(
+      ybase[oy] = (uint16_t)px_chain<TRC, TM, DESAT, LP, DBG, FB>(
           F, cv, pq_lds, pqi_lds, eq_lds, lut8v, spread_lds, lut, K, ybs, U, V, di, oyv, ozv, LP ? qo[s & 3] : 0.5f, ydq, dv);
       chroma_out(s, oyv, ozv);   // (BICUBIC: this pixel's Cb, Cr into the 4:4:4 scratch)
     }
@@ -1594,9 +1650,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
 
   const int pl = __builtin_amdgcn_readfirstlane(t >> 6) & 1, rem = t & 63;   // chroma store role (t < 128)
   const bool cst = t < 128 && !F.chr444;
-  for (;;) {
-    H2S_MARK("tile: commit, prefetch");
+  // ---- commit the loaded tile's registers to LDS (tile: its index) ----
+  // The loop below is rotated: the first tile is committed ahead of it and
+  // every later one at the loop's end, behind the previous tile's stores.
+  // There the vector-memory operations in flight are, oldest first, this
+  // tile's loads, then the two stores every thread has just issued (the store
+  // rule, put_luma), so the compiler's counted waits for the loads leave the
+  // stores outstanding: no wave waits for a write acknowledgement.  (With the
+  // commit at the loop's top, the entry from the prologue, where no store
+  // follows the loads, made the same waits drain the stores.)
+  auto commit = [&](unsigned ti) {
+    H2S_MARK("tile: commit");
     // ---- commit this tile's registers to LDS ----
+    if constexpr (SEMI && S420) {
+      if (!F.in_semi) cur.uh = halo_half(F, geo, t, cur.uh);   // (geo: the tile being committed)
+    }
     if (F.in_mask2 != 0xFFFFFFFFu) {   // h2s_lp_p010 TRUNCATE, semi-planar words (block-uniform)
       // semi-planar: the code sits in each 16-bit word's high bits; both
       // halves of a pair move down together and the mask (always set then)
@@ -1611,7 +1679,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       if constexpr (SUB == 2) mask_in(cur.va);
       else cur.uh &= F.in_mask2;
     }
-    const float my = stage_luma<YST>(yin, cur.ya, t >> 3, t & 7, ysc, yoff);
+    const float my = stage_luma(yin, cur.ya, t >> 3, t & 7, ysc, yoff);
     float mc = 0.0f;
     if constexpr (SUB == 1) {
       mc = stage_chroma422(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
@@ -1622,8 +1690,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     } else if ((t & 127) < 72) {
       mc = stage_chroma<HST>(hrow[__builtin_amdgcn_readfirstlane(t >> 7)], cur.ua, cur.uh, t & 127, cmid);
     }
+    // every thread waits for its chroma registers here, with or without a
+    // chunk to commit: none stays in flight into the next prefetch, where
+    // reusing the register would wait for it behind the stores
+    if constexpr (SUB == 2) asm volatile("" ::"v"(cur.ua.w), "v"(cur.va.w));
+    else asm volatile("" ::"v"(cur.ua.w), "v"(cur.uh));
+    if ((my > F.safe_y || mc > F.safe_c)) tflag[ti & 1u] = 1;
+  };
+  commit(tile);
+  for (;;) {
+    H2S_MARK("tile: prefetch");
     const int par = (int)(tile & 1u);
-    if ((my > F.safe_y || mc > F.safe_c)) tflag[par] = 1;
     const TileGeo g = geo;
     const bool more = tile + 1 < tend;   // block-uniform
     if (more) {
@@ -1631,7 +1708,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
       cur = tile_load<SEMI, SUB>(F, geo, t, lofs);  // in flight during this tile's compute
     }
     __syncthreads();
-    const bool fb = __builtin_amdgcn_readfirstlane(tflag[par]) == 0 && !F.chr444;
+    // (a product instance's bottom tile with rows past the frame: the
+    // exact-capable body, which skips their steps -- the same output)
+    const bool fb = __builtin_amdgcn_readfirstlane(tflag[par]) == 0 && !F.chr444 && !(DBG == 0 && g.py0 + TBH > F.H);
     if (t == 0) tflag[par ^ 1] = 0;   // for the next tile: read by every wave of the previous one before this barrier
     if (fb)
       steps(g, std::integral_constant<bool, true>{});
@@ -1641,16 +1720,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? H2S_TI
     __syncthreads();
 
     // ---- write the tile: 16-byte (u16) / 8-byte (u8) non-temporal stores ----
-    put_luma(F, g, read_luma<YST>(F, yin, t >> 3, t & 7), t >> 3, lofs.sy, 0);
+    put_luma(F, g, read_luma(F, yin, t >> 3, t & 7), t >> 3, lofs.sy, t);
+    // the chroma store of every thread (the store rule above put_luma): the
+    // threads with a chroma role read and quantise their chunk, the others
+    // (and rows past the frame) store nothing at ST_DROP
+    const bool osemi = SEMI && F.out_semi;   // block-uniform
+    u4v cv{0u, 0u, 0u, 0u};
+    int cvo = ST_DROP;
     if (cst) {
-      if (SEMI && F.out_semi)   // block-uniform
-        put_chroma_semi(F, g, read_chroma_semi(F, csum[0], t >> 3, t & 7), t >> 3, lofs.sc);
-      else
-        put_chroma(F, g, read_chroma(F, csum[0], pl, rem >> 2, rem & 3), pl, rem >> 2, lofs.sc);
+      const int cr = osemi ? t >> 3 : rem >> 2;
+      cv = osemi ? read_chroma_semi(F, csum[0], cr, t & 7) : read_chroma(F, csum[0], pl, cr, rem & 3);
+      if (g.cy0 + cr < F.ch) cvo = lofs.sc;
     }
+    put_chroma(F, g, cv, osemi ? 0 : pl, osemi, cvo, t);
     if (!more) break;
-    ++tile;
-    __syncthreads();   // the store phase has read yin / csum before they are refilled
+    commit(++tile);
+    // No barrier before that commit.  What it writes before the next tile's
+    // barrier 1 is ordered without one, for every instance form: the luma slot
+    // (row t >> 3, chunk t & 7) is the slot this same thread has just read in
+    // read_luma (a wave's LDS operations execute in order); hrow (4:2:0 rows,
+    // the SUB 1 / 2 windows, the semi-planar rows alike) was last read in the
+    // steps, before barrier 2; tflag[par ^ 1] was zeroed by thread 0 before
+    // barrier 2 and is read after the next barrier 1.  csum, and yin by other
+    // threads, are next written in the next tile's steps, behind its barrier
+    // 1, which no wave passes before every wave has issued the stores above,
+    // i.e. has its store-phase reads of yin and csum back.  The libplacebo and
+    // debug instances and the BICUBIC scratch path keep nothing else in LDS
+    // across tiles
   }
 }
 
