@@ -340,6 +340,11 @@ KParams frame_range(const KParams& k, int f0, int n) {
 // the width the tile kernel covers: the whole 64-pixel tiles
 static int tiled_width(const KParams& k) { return k.W & ~(h2s::TBW - 1); }
 
+// the k_tile instance that converts k's frames (k: resolved, geometry filled)
+static h2s::TileKey tile_key_of(const KParams& k, bool dbg) {
+  return h2s::tile_key(k, k.in_cstep == 2 || k.out_cstep == 2, dbg);
+}
+
 // the tile kernel over the whole 64-pixel tiles of k's frames
 hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& r, const TileOpts& o) {
   FastParams F;
@@ -383,10 +388,7 @@ hipError_t launch_tiles(const h2s_ctx* c, const KParams& k, const Route& r, cons
     F.safe_y = F.safe_c = HUGE_VALF;
     F.log2_lin_scale = F.log2_pq_scale;
   }
-  const int desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
-  // (top-left 4:2:0: the SUB 3 instances, h2s_fast_tl.hip / h2s_fast_lp_tl.hip)
-  return h2s::launch_fast(F, k.dovi ? 2 : k.transfer, k.tonemap, desat, k.pipe == h2s::PIPE_LIBPLACEBO ? 1 : 0, r.s,
-                          k.vco ? 3 : k.sub);
+  return h2s::launch_fast(F, tile_key_of(k, o.dbg != 0), r.s);
 }
 
 // the generic kernel over a column range of k's frames (enum Columns, h2s_host.h)
@@ -439,7 +441,7 @@ hipError_t launch_route(const h2s_ctx* c, const KParams& k, const Route& r) {
 // tile and 16-byte aligned rows
 static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
   const h2s_params& p = c->params;
-  if (!c->fast_enabled || !h2s::fast_supported(k.tonemap)) return false;
+  if (!c->fast_enabled || !h2s::tile_instance(tile_key_of(k, false))) return false;
   // Dolby Vision records: the tile kernel takes the shape profile 5 carries (dovi_tile_shape,
   // h2s_api_dovi.hip); any other record runs on the generic kernel
   if (k.dovi && !c->dovi_tile) return false;
@@ -840,11 +842,11 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   const Route r{choose_path(c, k, &din, &fo, out8, c->in_fmt, PLANAR_420), false, out8, c->in_fmt, PLANAR_420, s};
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
-  // (4:2:0 input: there are no debug instances of the tile kernel for 4:2:2 /
-  // 4:4:4 input or for a top-left set, whose planes are the generic kernel's
-  // whatever the path; a full-range set changes constants only)
+  // (where it has one: there are no debug instances of the tile kernel for
+  // 4:2:2 / 4:4:4 input or for a top-left set, whose planes are the generic
+  // kernel's whatever the path; a full-range set changes constants only)
   e = h2s::launch_debug(k, stage, dout, s);
-  if (e == hipSuccess && r.tile() && c->in_fmt.sub == H2S_SUB_420 && !c->in_fmt.vco()) {
+  if (e == hipSuccess && r.tile() && h2s::tile_instance(tile_key_of(k, true))) {
     if (k.lut_enabled && (rc = ensure_lut_yuv(c, k, s))) {
       hipStreamSynchronize(s);
       return rc;

@@ -54,7 +54,7 @@ std::string record_error(const h2s_dovi_rpu& r, int i) {
 }
 
 // the shape profile 5 actually carries, which the tile kernel's Dolby Vision
-// instances take (h2s_tile.h dovi_tile_front): luma polynomial pieces only, each
+// instances take (h2s_tile_px.h dovi_tile_front): luma polynomial pieces only, each
 // chroma component a single piece (polynomial, or MMR up to order 3)
 bool dovi_tile_shape(const h2s_dovi_rpu& r) {
   for (int p = 0; p < r.comp[0].num_pivots - 1; p++)

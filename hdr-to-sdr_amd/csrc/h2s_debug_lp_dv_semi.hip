@@ -1,12 +1,4 @@
-// h2s_debug_lp_dv_semi.hip — the tile kernel's Dolby Vision profile-5 debug instances (DBG = 1) for semi-planar frame sets
-// (k_tile<2, TM, 0, 1, ...>: the libplacebo branch's five operators), in a
-// translation unit of their own so that the parallel build stays parallel.
-#include <hip/hip_runtime.h>
+// h2s_debug_lp_dv_semi.hip — the Dolby Vision profile-5 debug instances of k_tile for semi-planar frame sets.
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_DV_INSTANCE(1, true)
-
-}  // namespace h2s
+H2S_TILE_UNIT(debug_lp_dv_semi)

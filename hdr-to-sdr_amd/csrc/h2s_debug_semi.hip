@@ -1,12 +1,4 @@
-// h2s_debug_semi.hip — the CPU chain's debug instances of k_tile (DBG = 1, as
-// h2s_debug.hip) for semi-planar input (h2s_debug_float under
-// h2s_set_frame_layout).
-#include <hip/hip_runtime.h>
+// h2s_debug_semi.hip — the CPU chain's debug instances of k_tile for semi-planar frame sets.
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_INSTANCE(1, 0, true)
-
-}  // namespace h2s
+H2S_TILE_UNIT(debug_semi)

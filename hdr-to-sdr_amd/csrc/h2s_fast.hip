@@ -1,31 +1,16 @@
-// h2s_fast.hip — launcher of the tile kernel (h2s_tile.h): the product
-// instances, the dispatch over every instance, and the Y'CbCr lattice build.
+// h2s_fast.hip — launcher of the tile kernel (h2s_tile.h): the CPU chain's
+// planar product instances, the key, predicate and dispatch over every
+// instance set (h2s_tile_sets.h), and the Y'CbCr lattice build.
 #include <hip/hip_runtime.h>
 
-#include "h2s_launch.h"
-#include "h2s_tile.h"
+#include "h2s_tile_sets.h"
+
+H2S_TILE_UNIT(fast)   // the CPU chain's product instances for planar frame sets
 
 namespace h2s {
 
-H2S_TILE_INSTANCE(0, 0, false)
-H2S_TILE_EXTERN(0, 1, false)     // h2s_fast_lp.hip
-H2S_TILE_EXTERN(0, 0, true)      // h2s_fast_semi.hip: the instances for semi-planar frame sets
-H2S_TILE_EXTERN(0, 1, true)      // h2s_fast_lp_semi.hip
-H2S_TILE_EXTERN(0, 0, true, 1)   // h2s_fast_sub422.hip: 4:2:2 input
-H2S_TILE_EXTERN(0, 0, true, 2)   // h2s_fast_sub444.hip: 4:4:4 input
-H2S_TILE_EXTERN(0, 0, true, 3)   // h2s_fast_tl.hip: top-left 4:2:0 input
-H2S_TILE_EXTERN(0, 1, true, 3)   // h2s_fast_lp_tl.hip
-H2S_TILE_EXTERN(1, 0, false)     // h2s_debug.hip: the debug instances
-H2S_TILE_EXTERN(1, 1, false)     // h2s_debug_lp.hip
-H2S_TILE_EXTERN(1, 0, true)      // h2s_debug_semi.hip
-H2S_TILE_EXTERN(1, 1, true)      // h2s_debug_lp_semi.hip
-H2S_TILE_DV_EXTERN(0, false)     // h2s_fast_lp_dv.hip: the Dolby Vision profile-5 instances (TRC 2)
-H2S_TILE_DV_EXTERN(0, true)      // h2s_fast_lp_dv_semi.hip
-H2S_TILE_DV_EXTERN(1, false)     // h2s_debug_lp_dv.hip
-H2S_TILE_DV_EXTERN(1, true)      // h2s_debug_lp_dv_semi.hip
-
 // YUV-premultiplied lattice (12-byte records, .cube order):
-// ((16 + 219*Y)*s + 0.5, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
+// ((16 + 219*Y)*s, 224*s*Cb/4, 224*s*Cr/4) with Y, Cb, Cr the BT.709
 // values of the clamped RGB lattice point, in the oracle's S6 operation order.
 __global__ void k_build_lut_yuv(const float4* rgb, float* yuv, int n3, const YuvLutConsts K) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -40,24 +25,60 @@ __global__ void k_build_lut_yuv(const float4* rgb, float* yuv, int n3, const Yuv
     yuv[3 * i] = c.x, yuv[3 * i + 1] = c.y, yuv[3 * i + 2] = c.z;
     return;
   }
-  // (H2S_EQMAGIC: no +0.5, k_tile rounds to nearest instead)
-  yuv[3 * i] = (16.0f + 219.0f * Y) * s + (H2S_EQMAGIC ? 0.0f : 0.5f);
+  // the luma record's rounding offset: none (k_tile rounds to nearest instead, px_chain's EQM)
+  constexpr float Y_ROUND = 0.0f;
+  yuv[3 * i] = (16.0f + 219.0f * Y) * s + Y_ROUND;
   yuv[3 * i + 1] = 224.0f * s * 0.25f * cb;
   yuv[3 * i + 2] = 224.0f * s * 0.25f * cr;
 }
 
-bool fast_supported(int tonemap) { return tonemap >= 4 && tonemap <= 8; }
+// The key of the launch that converts k's frames: dbg, the chain's debug
+// instance (which also writes the planes of F.dbg_stage); semi, a semi-planar
+// set on either side.
+// trc 2: Dolby Vision records (h2s_set_dovi), the k_tile<2, ...> instances.
+// desat: 0 off, 1 weighted luma, 2 RGB-coefficient luma (vf_tonemap's;
+// BT.2390, spline and the libplacebo branch's curves have none).
+// sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4), or 3 = 4:2:0
+// sited top-left (h2s_set_input_tags); those sets are SEMI instances whatever
+// the layouts are
+TileKey tile_key(const KParams& k, bool semi, bool dbg) {
+  TileKey t;
+  t.trc = k.dovi ? 2 : k.transfer;
+  t.tm = k.tonemap;
+  t.lp = k.pipe == PIPE_LIBPLACEBO ? 1 : 0;
+  t.desat = !k.desat_on ? 0 : (k.lr == 1.0f && k.lg == 1.0f && k.lb == 1.0f ? 2 : 1);
+  if (t.tm == 7 || t.tm == 8 || t.lp) t.desat = 0;
+  t.dbg = dbg ? 1 : 0;
+  t.sub = k.vco ? 3 : k.sub;
+  t.semi = semi || t.sub ? 1 : 0;
+  return t;
+}
 
-// desat: 0 off, 1 weighted luma, 2 RGB-coefficient luma (vf_tonemap's; the
-// libplacebo curves have none).  lp: the libplacebo branch (every operator).
-// F.dbg_stage: 0 = the product kernel; 1..5 = the chain's debug instance, which
-// also writes that h2s_stage's planes (F.dbg set)
-// trc 2: a launch with Dolby Vision records (h2s_set_dovi), the k_tile<2, ...> instances
-// sub: the input's chroma subsampling (1 = 4:2:2, 2 = 4:4:4: CPU chain product
-// instances only; anything else there is an error, never another kernel), or
-// 3 = 4:2:0 sited top-left (h2s_set_input_tags): either chain's product
-// instances, planar or semi-planar sets; there are no debug instances
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub) {
+namespace {
+
+struct TileSet {
+  int dbg, lp, semi, sub, family;
+  hipError_t (*launch)(const FastParams&, const TileKey&, dim3, size_t, hipStream_t);
+};
+const TileSet SETS[] = {
+#define S(UNIT, DBG, LP, SEMI, SUB, FAMILY) {DBG, LP, SEMI, SUB, FAMILY_##FAMILY, launch_set<SET_##UNIT>},
+    H2S_TILE_SETS(S)
+#undef S
+};
+
+// the set that holds k's instance; none: there is no such instance
+const TileSet* set_of(const TileKey& k) {
+  for (const TileSet& r : SETS)
+    if (r.dbg == k.dbg && r.lp == k.lp && r.semi == k.semi && r.sub == k.sub && family_case(r.family, k)) return &r;
+  return nullptr;
+}
+
+}  // namespace
+
+bool tile_instance(const TileKey& k) { return set_of(k) != nullptr; }
+
+// a key without an instance is an error, never another kernel
+hipError_t launch_fast(const FastParams& F, const TileKey& k, hipStream_t s) {
   const long long nt = (long long)F.nbx * F.nby * F.nframes;
   if (nt == 0) return hipSuccess;
   const long long nb = (nt + F.tpb - 1) / F.tpb;
@@ -66,32 +87,8 @@ hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, 
   // allocation, measured +4 % and +42 % on the bench content:
   // profiles/r03/ablations/blocks_per_cu.log)
   const size_t lds = ((size_t)F.eq_n * sizeof(uint16_t) + 15) & ~(size_t)15;
-  if (tm == 7 || tm == 8 || lp) desat = 0;
-  const bool dbg = F.dbg_stage != 0;
-  if (trc == 2) {   // Dolby Vision records (F.dovi): the libplacebo branch, left-sited 4:2:0; anything else is an error
-    if (!lp || sub || !F.dovi) return hipErrorInvalidValue;
-    const bool dsemi = F.in_semi || F.out_semi;
-    auto* dlaunch = dbg ? (dsemi ? launch_tile_dv<1, true> : launch_tile_dv<1, false>)
-                        : (dsemi ? launch_tile_dv<0, true> : launch_tile_dv<0, false>);
-    return dlaunch(F, tm, grid, lds, s);
-  }
-  if (sub == 3) {
-    if (dbg) return hipErrorInvalidValue;
-    return lp ? launch_tile<0, 1, true, 3>(F, trc, tm, desat, grid, lds, s)
-              : launch_tile<0, 0, true, 3>(F, trc, tm, desat, grid, lds, s);
-  }
-  if (sub) {
-    if (lp || dbg || F.in_semi || sub > 2) return hipErrorInvalidValue;
-    return sub == 1 ? launch_tile<0, 0, true, 1>(F, trc, tm, desat, grid, lds, s)
-                    : launch_tile<0, 0, true, 2>(F, trc, tm, desat, grid, lds, s);
-  }
-  // planar sets on both sides: the instances without the layout branches
-  const bool semi = F.in_semi || F.out_semi;
-  auto* launch = dbg ? (lp ? (semi ? launch_tile<1, 1, true> : launch_tile<1, 1, false>)
-                           : (semi ? launch_tile<1, 0, true> : launch_tile<1, 0, false>))
-                     : (lp ? (semi ? launch_tile<0, 1, true> : launch_tile<0, 1, false>)
-                           : (semi ? launch_tile<0, 0, true> : launch_tile<0, 0, false>));
-  return launch(F, trc, tm, desat, grid, lds, s);
+  const TileSet* set = set_of(k);
+  return set ? set->launch(F, k, grid, lds, s) : hipErrorInvalidValue;
 }
 
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st) {

@@ -1,14 +1,5 @@
-// h2s_fast_lp.hip — the tile kernel's product instances for the libplacebo
-// branch (k_tile<..., LP = 1>), in their own translation unit so that they
-// compile with LLVM's default scheduler, which measured 2-3 % faster for them
-// than the max-memory-clause schedule the CPU chain's instances use
-// (profiles/r03/ablations/fast_body_scheduler_*.log).
-#include <hip/hip_runtime.h>
+// h2s_fast_lp.hip — the libplacebo branch's product instances of k_tile: their own unit, so that they compile
+// with LLVM's default scheduler, 2-3 % faster for them (profiles/r03/ablations/fast_body_scheduler_*.log).
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_INSTANCE(0, 1, false)
-
-}  // namespace h2s
+H2S_TILE_UNIT(fast_lp)

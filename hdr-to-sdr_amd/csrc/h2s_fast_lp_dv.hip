@@ -1,12 +1,4 @@
-// h2s_fast_lp_dv.hip — the tile kernel's Dolby Vision profile-5 product instances, planar sets
-// (k_tile<2, TM, 0, 1, ...>: the libplacebo branch's five operators), in a
-// translation unit of their own so that the parallel build stays parallel.
-#include <hip/hip_runtime.h>
+// h2s_fast_lp_dv.hip — the Dolby Vision profile-5 product instances of k_tile.
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_DV_INSTANCE(0, false)
-
-}  // namespace h2s
+H2S_TILE_UNIT(fast_lp_dv)

@@ -1,11 +1,4 @@
-// h2s_fast_lp_semi.hip — the libplacebo branch's product instances of the
-// tile kernel for semi-planar frame sets (k_tile<..., LP = 1, 0, SEMI = true>).
-#include <hip/hip_runtime.h>
+// h2s_fast_lp_semi.hip — the libplacebo branch's product instances of k_tile for semi-planar frame sets.
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_INSTANCE(0, 1, true)
-
-}  // namespace h2s
+H2S_TILE_UNIT(fast_lp_semi)

@@ -1,13 +1,4 @@
-// h2s_fast_semi.hip — the CPU chain's product instances of the tile kernel
-// for semi-planar frame sets (k_tile<..., SEMI = true>: nv12 / p010le / p012le
-// on either side, h2s_set_frame_layout), apart from the planar ones so that
-// those stay exactly what they were (h2s_tile.h).
-#include <hip/hip_runtime.h>
+// h2s_fast_semi.hip — the CPU chain's product instances of k_tile for semi-planar frame sets.
+#include "h2s_tile_sets.h"
 
-#include "h2s_tile.h"
-
-namespace h2s {
-
-H2S_TILE_INSTANCE(0, 0, true)
-
-}  // namespace h2s
+H2S_TILE_UNIT(fast_semi)

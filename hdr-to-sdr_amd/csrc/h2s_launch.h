@@ -33,9 +33,15 @@ hipError_t launch_peak_stats(const KParams& P, float2* partial, const PeakTail& 
 hipError_t launch_peak_curves(double2* fstat, int n, const PeakModel& M, PeakState* st, CurveConsts* out,
                               hipStream_t s);
 
-// h2s_fast.hip
-bool fast_supported(int tonemap);
-hipError_t launch_fast(const FastParams& F, int trc, int tm, int desat, int lp, hipStream_t s, int sub = 0);
+// h2s_fast.hip.  TileKey: which k_tile<TRC, TM, DESAT, LP, DBG, SEMI, SUB>
+// a launch takes (tile_key builds it from the resolved parameters;
+// tile_instance: there is such an instance, h2s_tile_sets.h's table)
+struct TileKey {
+  int trc, tm, desat, lp, dbg, semi, sub;
+};
+TileKey tile_key(const KParams& k, bool semi, bool dbg);
+bool tile_instance(const TileKey& k);
+hipError_t launch_fast(const FastParams& F, const TileKey& k, hipStream_t s);
 hipError_t build_lut_yuv(const float4* rgb, float* yuv, int n, const YuvLutConsts& K, hipStream_t st);
 
 // h2s_preview.hip (the tap tables: resize_taps, h2s_resolve.hip; one width per axis)

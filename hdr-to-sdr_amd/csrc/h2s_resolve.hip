@@ -299,7 +299,7 @@ void resolve(const h2s_params* p, KParams* k, std::vector<uint16_t>* eq) {
 }
 
 // ST 2084 inverse EOTF (y = luminance / 10000 -> E) as PQI_NSEG cubic
-// segments for the tile kernel's IPT form (h2s_tile.h pqi): segment s covers
+// segments for the tile kernel's IPT form (h2s_tile_tone.h pqi): segment s covers
 // y = 2^e (1 + j/8 + t), e = PQI_OCT0 + s/8, j = s%8, t in [0, 1/8), read from
 // the float's exponent and top three mantissa bits; the cubic in t through
 // the exact (double) encode at the 4 Chebyshev nodes (relative error <=

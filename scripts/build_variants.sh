@@ -1,6 +1,10 @@
 #!/bin/bash
 # Build libh2s variants for scripts/time_variants.py.
 # Usage: bash scripts/build_variants.sh NAME:"-DFLAG ..." NAME2:"..."
+# (The flags reach the product source as it is.  The tile kernel's decided
+# switches -- H2S_TAGSEL, H2S_EQMAGIC, H2S_YST*, H2S_NT_*, H2S_TILE_WPE* -- are
+# no longer in it: build those variants with scripts/build_ablation.sh and
+# profiles/tile_split/ab_patches/tile_switches.patch.)
 # Only the product tile instances (h2s_fast.hip, h2s_fast_lp.hip) are rebuilt
 # with the flags;
 # every other object comes from the in-tree build (hdr-to-sdr_amd/build/obj,

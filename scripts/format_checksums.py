@@ -64,6 +64,16 @@ A Dolby Vision record set (three luma maps, tests/dovi_ref.py) goes through
 the row form at 208x64, planar PQ 10-bit.
 
   [H2S_LIB=...] python scripts/format_checksums.py --peak OUT.json
+
+--tile-sets OUT.json instead makes one launch per instance of the tile kernel
+(tests/tile_sets_ref.py ROWS: each set x its transfers x operators x desat
+settings; the Dolby Vision sets with a full-order record): 192x96, 2 frames,
+device sets, {"set/transfer/operator/desat": [h2s_query_path, sha256]}; a debug
+set's hash is of its stage-5 planes.  Two builds whose lines are equal route
+every launch to the same instance: one that took a neighbouring instance
+changes bytes or path.
+
+  [H2S_LIB=...] python scripts/format_checksums.py --tile-sets OUT.json
 """
 import ctypes
 import dataclasses
@@ -264,9 +274,45 @@ def peak(path):
     return 0
 
 
+def tile_sets(path):
+    import tile_sets_ref as TS
+    import torch
+
+    import hdr2sdr
+    from hdr2sdr.frames import FrameBatch
+
+    lattice = hdr2sdr.generate_lattice(TS.LUT_N)
+    record = TS.dovi_record()
+    srcs = {name: src.to_torch('cuda') for name, (src, _) in TS.sources(TS.base_source()).items()}
+    res = {}
+    tm = hdr2sdr.Tonemapper(0)
+    for row in TS.ROWS:
+        s = row[0]
+        tm.set_params(TS.params(row))
+        tm.set_lut(lattice)
+        tm.set_dovi(record if s.chain == 'dv' else None)
+        src = srcs[s.name]
+        dst = FrameBatch.empty_torch(TS.NF, TS.W, TS.H, TS.BITS, 'cuda', 'planar' if s.debug else s.layout)
+        dst.buf.fill_(0x5555)
+        route = tm.query_path(src, dst)
+        if s.debug:
+            out = tm.debug_float(src, TS.DEBUG_STAGE)
+        else:
+            tm.process(src, dst)
+            torch.cuda.synchronize()
+            out = dst.to_numpy().buf
+        res[TS.row_id(row)] = [route, _sha(out)]
+    tm.set_dovi(None)
+    tm.close()
+    _write(res, path)
+    return 0
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == '--peak':
         return peak(sys.argv[2])
+    if len(sys.argv) == 3 and sys.argv[1] == '--tile-sets':
+        return tile_sets(sys.argv[2])
     if len(sys.argv) == 3 and sys.argv[1] == '--debug-planes':
         return debug_planes(sys.argv[2])
     if len(sys.argv) == 3 and sys.argv[1] == '--preview':

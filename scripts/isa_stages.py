@@ -1,5 +1,5 @@
 """Per-stage instruction and slot table of one k_tile instance, from an ISA
-listing built with -DH2S_ISA_MARKS (h2s_tile.h H2S_MARK: each marker is an
+listing built with -DH2S_ISA_MARKS (h2s_tile_tone.h H2S_MARK: each marker is an
 assembler comment ";@@name" that opens stage `name`).
 
 The listing's basic blocks are laid out by the compiler, not in source

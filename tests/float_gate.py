@@ -48,7 +48,7 @@ FLOAT_CFGS = {
 # share of kept values that fail 1e-3 relative and pass only through a floor
 # or conditioning term, per content (the report's floor_only_frac)
 FLOOR_ONLY_MAX = {'ramp': 0.06, 'edges': 0.05, 'uniform': 0.03, 'smooth': 0.02}
-TILE_DARK_EXACT = True    # k_tile evaluates its PQ table's first segment exactly (h2s_tile.h dark re-run): no table floor
+TILE_DARK_EXACT = True    # k_tile evaluates its PQ table's first segment exactly (h2s_tile_px.h lin_tone, the dark re-run): no table floor
 EPS_IPT = 2e-5            # LMS relative error of the IPT form on the tile kernel (tests/diag/diag_ipt.py: max 1.33e-5, round 5)
 TIE_WINDOW = 0.25         # download codes: a flip must sit this close to the rounding boundary (measured max 0.16)
 

@@ -28,3 +28,19 @@ def test_a_flag_change_rebuilds(tmp_path, monkeypatch):
     monkeypatch.setattr(_build, 'CFLAGS', _build.CFLAGS + ['-DH2S_FLAG_CHANGED'])
     with pytest.raises(_Compiled):
         _build.build_lib()
+
+
+def test_every_included_project_header_is_a_build_dependency():
+    """A header that csrc/ includes and HEADERS lacks would leave objects
+    current after an edit to it."""
+    import glob
+    import os
+    import re
+
+    included = set()
+    for path in glob.glob(os.path.join(_build.CSRC, '*')):
+        with open(path, encoding='utf-8') as fh:
+            included.update(re.findall(r'^\s*#\s*include\s+"(h2s_[^"]+\.h)"', fh.read(), re.M))
+    assert included, 'no project header found: the pattern no longer matches the sources'
+    assert sorted(included - set(_build.HEADERS)) == []
+    assert all(os.path.exists(os.path.join(_build.CSRC, h)) for h in _build.HEADERS)
