@@ -7,7 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "h2s_device.h"
+#include "h2s_params.h"
 
 namespace h2s {
 

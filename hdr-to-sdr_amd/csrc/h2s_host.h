@@ -22,8 +22,8 @@
 
 #define H2S_PRIVATE_TEST_HOOKS
 #include "../../include/h2s.h"
-#include "h2s_device.h"
 #include "h2s_launch.h"
+#include "h2s_params.h"
 #include "h2s_peak.h"
 #include "h2s_srcprev.h"
 

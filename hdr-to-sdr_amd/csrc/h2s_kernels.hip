@@ -10,12 +10,13 @@
 // columns fastest, so a wavefront reads contiguous row segments (16-B Y loads,
 // 8-B chroma loads per lane).  Blocks are remapped so that each XCD walks a
 // contiguous range of rows (chroma halo rows and LUT lines stay in its L2;
-// xcd_remap, h2s_device.h).
+// xcd_remap, h2s_math.h).
 #include <hip/hip_runtime.h>
 
-#include "h2s_device.h"
 #include "h2s_launch.h"
 #include "h2s_lpx.h"
+#include "h2s_math.h"
+#include "h2s_params.h"
 
 namespace h2s {
 

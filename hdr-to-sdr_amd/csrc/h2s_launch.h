@@ -9,7 +9,7 @@
 
 namespace h2s {
 
-struct KParams;           // h2s_device.h
+struct KParams;           // h2s_params.h
 struct FastParams;
 struct CurveConsts;
 struct YuvLutConsts;

@@ -11,18 +11,21 @@
 // ragged columns, N > 177 lattices, BICUBIC two-pass).  The tile kernel's
 // float32 form lands within its stated bound of these values
 // (tests/lp_gate.py).  Stage 4 on (lut3d's 8-bit path on the integer codes,
-// Y'CbCr) is the float arithmetic of h2s_device.h, as the oracle's.
+// Y'CbCr) is the float arithmetic of h2s_chain.h, as the oracle's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
 
-#include "h2s_device.h"
+#include "h2s_chain.h"
 #include "h2s_dovi.h"
 
 namespace h2s {
 
 // ST 2084 in double (normalised, 1 = 10000 nits): zimg's EOTF (denominator
-// floored at FLT_MIN; past the pole +inf, as the float form) and the inverse
+// floored at FLT_MIN; past the pole +inf, as the float form) and the inverse.
+// pqx_eotf stays its own function: the other double forms (hd_pq_eotf in
+// h2s_math.h, pq_eotf_dd in h2s_chain.h) neither floor the denominator nor
+// saturate to +inf
 __device__ __forceinline__ double pqx_eotf(double e) {
   if (!(e > 0.0)) return 0.0;
   const double xp = pow(e, 1.0 / (double)PQ_M2);
@@ -243,7 +246,7 @@ __device__ __forceinline__ void lpx_chain(const KParams& P, const LpX& X, double
       const double v = e[k] < 0.0 ? 0.0 : (e[k] > 1.0 ? 1.0 : e[k]);
       q[k] = (float)floor(v * (double)P.lp_qs + off) * (1.0f / 255.0f);
     }
-    // vf_lut3d's 8-bit path on the codes (h2s_device.h lut3d_8bit after its rounding)
+    // vf_lut3d's 8-bit path on the codes (h2s_chain.h lut3d_8bit after its rounding)
     float lr = q[0], lg = q[1], lb = q[2];
     lut3d_tetra(P, lr, lg, lb);
     const float sf = 1.0f / 255.0f;

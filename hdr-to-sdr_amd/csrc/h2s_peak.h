@@ -3,7 +3,9 @@
 // is DESIGN.md §4.6), as host/device code: the percentile of a frame's
 // PQ(max R,G,B) histogram, the IIR over frames with the scene-change bypass,
 // and the BT.2390 / spline / libplacebo-NORM curve constants of the smoothed
-// peak in the tile kernel's folded form (CurveConsts).
+// peak in the tile kernel's folded form (CurveConsts).  The double-precision
+// ST 2084 forms and Hable's curve that the set-ups call are h2s_math.h's; the
+// generic kernel's chain (h2s_chain.h) is not needed here.
 //
 // One definition serves the host (the static curve of h2s_set_params) and the
 // device (k_peak_stats* + k_peak_finish in h2s_peak.hip: h2s_process with
@@ -16,11 +18,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "h2s_device.h"
+#include "h2s_math.h"
+#include "h2s_params.h"
 
 namespace h2s {
 
-constexpr int PEAK_BLOCKS = 128;      // partial (max, sum) records per frame (k_peak_stats*), default (round 6: 64 -> 128)
+constexpr int PEAK_BLOCKS = 128;      // partial (max, sum) records per frame (k_peak_stats*), default
 constexpr int PEAK_BLOCKS_MAX = 256;  // ... at most (H2S_OPT_TEST_PEAK_BLOCKS A/B; one per finish thread)
 constexpr int PEAK_BINS = 1024;  // percentile histogram bins over PQ [0, 1]
 
@@ -66,29 +69,8 @@ struct PeakTail {
   int nframes;
 };
 
-__host__ __device__ inline double hd_pq_encode(double y) {
-  const double m1 = 0.1593017578125, m2 = 78.84375, c1 = 0.8359375, c2 = 18.8515625, c3 = 18.6875;
-  const double ym = pow(fmax(y, 0.0), m1);
-  return pow((c1 + c2 * ym) / (1.0 + c3 * ym), m2);
-}
-
-// ST 2084 EOTF in double (normalised: 1.0 = 10000 nits)
-__host__ __device__ inline double hd_pq_eotf(double e) {
-  const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0, c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0,
-               c3 = 2392.0 / 4096.0 * 32.0;
-  if (!(e > 0.0)) return 0.0;
-  const double xp = pow(e, 1.0 / m2);
-  const double num = xp - c1 > 0.0 ? xp - c1 : 0.0;
-  return pow(num / (c2 - c3 * xp), 1.0 / m1);
-}
-
 __host__ __device__ inline PqRefs pq_refs(double t_white, double t_black) {
   return PqRefs{hd_pq_encode(0.0), hd_pq_encode(t_white / 10000.0), hd_pq_encode(t_black / 10000.0)};
-}
-
-__host__ __device__ inline float hd_hable(float in) {
-  const float a = 0.15f, b = 0.50f, c = 0.10f, d = 0.20f, e = 0.02f, f = 0.30f;
-  return (in * (in * a + b * c) + d * e) / (in * (in * a + b) + d * f) - e / f;
 }
 
 // libplacebo's reinhard / hable / mobius in NORM units (1 = target white) for
@@ -101,7 +83,7 @@ __host__ __device__ inline void lp_norm_consts(double peak, double tm_param, dou
   const float ct = isnan(tm_param) ? 0.5f : (float)tm_param;
   k->n_rein_off = (1.0f - ct) / ct;
   k->n_rein_scale = (pk + k->n_rein_off) / pk;
-  k->n_hable_inv = 1.0f / hd_hable(pk);
+  k->n_hable_inv = 1.0f / hable(pk);
   const float j = isnan(tm_param) ? 0.3f : (float)tm_param;
   const float a = -j * j * (pk - 1.0f) / (j * j - 2.0f * j + pk);
   const float b = (j * j - 2.0f * j * pk + pk) / fmaxf(1e-6f, pk - 1.0f);

@@ -5,6 +5,7 @@
 // libplacebo here, model in DESIGN.md).  PQ sources: PQ(max(EOTF(E))) ==
 // clamp(max(E), 0, 1) exactly, so no transcendental is needed.  Chroma is taken nearest.
 // grid = (M.nblocks, frames); partial[f * M.nblocks + b] = (max, sum) over block b's rows / chunks
+#include "h2s_chain.h"
 #include "h2s_dovi.h"
 #include "h2s_launch.h"
 #include "h2s_peak.h"

@@ -14,7 +14,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "h2s_device.h"
 #include "h2s_launch.h"
 #include "h2s_srcprev.h"
 

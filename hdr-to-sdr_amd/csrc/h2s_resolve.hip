@@ -7,6 +7,7 @@
 // and reasoned about, without a device; whatever allocates, copies, launches
 // or waits lives in h2s_api*.hip.
 #include "h2s_host.h"
+#include "h2s_math.h"
 
 using namespace h2s::host;
 using h2s::FastParams;
@@ -17,10 +18,6 @@ namespace host {
 
 // ---- parameter resolution (mirrors vf_tonemap init/filter_frame, zimg,
 // vf_eq create_lut; the CPU statement is oracle/h2s_oracle.c resolve()) ----
-static float hable_h(float in) { return h2s::hd_hable(in); }
-
-static double pq_encode_d(double y) { return h2s::hd_pq_encode(y); }
-
 int validate_params(h2s_ctx* c, const h2s_params* p) {
   if (p->transfer_in != H2S_TRC_PQ && p->transfer_in != H2S_TRC_HLG)
     return fail(c, H2S_E_INVALID_ARG, "transfer_in must be PQ or HLG");
@@ -203,7 +200,7 @@ void resolve(const h2s_params* p, KParams* k, std::vector<uint16_t>* eq) {
   k->gam_inv_param = (float)(1.0 / param);
   k->gam_low_k = (float)(pow(0.05 / peak, 1.0 / param) / 0.05);
   k->clip_k = (float)param;
-  k->hable_peak_inv = 1.0f / hable_h((float)peak);
+  k->hable_peak_inv = 1.0f / h2s::hable((float)peak);
   k->rein_p = (float)param;
   k->rein_k = (float)((peak + param) / peak);
   {
@@ -298,14 +295,9 @@ void resolve(const h2s_params* p, KParams* k, std::vector<uint16_t>* eq) {
   k->eq_identity = ident ? 1 : 0;
 }
 
-// ST 2084 inverse EOTF (y = luminance / 10000 -> E) as PQI_NSEG cubic
-// segments for the tile kernel's IPT form (h2s_tile_tone.h pqi): segment s covers
-// y = 2^e (1 + j/8 + t), e = PQI_OCT0 + s/8, j = s%8, t in [0, 1/8), read from
-// the float's exponent and top three mantissa bits; the cubic in t through
-// the exact (double) encode at the 4 Chebyshev nodes (relative error <=
-// 1.5e-7 with float32 coefficients).  Entry 0 is the constant PQ(0), read for
-// y <= 0 and for y below the first octave (2^-64, 1e-15 nits: PQ within 3e-7
-// of PQ(0)); segment s is entry 1 + s (PQI_NTAB entries)
+// ---- the cubic tables ----
+// the cubic c0 + c1 t + c2 t^2 + c3 t^3 through four points: the 4x4
+// Vandermonde system A c = y by Gaussian elimination (every table's solve)
 static void solve_cubic(const double t[4], const double y[4], double c[4]) {
   double A[4][5];
   for (int k = 0; k < 4; k++) {
@@ -326,16 +318,24 @@ static void solve_cubic(const double t[4], const double y[4], double c[4]) {
   for (int k = 0; k < 4; k++) c[k] = A[k][4] / A[k][k];
 }
 
+// ST 2084 inverse EOTF (y = luminance / 10000 -> E) as PQI_NSEG cubic
+// segments for the tile kernel's IPT form (h2s_tile_tone.h pqi): segment s covers
+// y = 2^e (1 + j/8 + t), e = PQI_OCT0 + s/8, j = s%8, t in [0, 1/8), read from
+// the float's exponent and top three mantissa bits; the cubic in t through
+// the exact (double) encode at the 4 Chebyshev nodes (relative error <=
+// 1.5e-7 with float32 coefficients).  Entry 0 is the constant PQ(0), read for
+// y <= 0 and for y below the first octave (2^-64, 1e-15 nits: PQ within 3e-7
+// of PQ(0)); segment s is entry 1 + s (PQI_NTAB entries)
 void build_pqi_table(std::vector<float4>* out) {
   constexpr int K = h2s::PQI_PER_OCT;
   out->resize(h2s::PQI_NTAB);
-  (*out)[0] = make_float4(0.0f, 0.0f, 0.0f, (float)pq_encode_d(0.0));
+  (*out)[0] = make_float4(0.0f, 0.0f, 0.0f, (float)h2s::hd_pq_encode(0.0));
   double t[4];
   for (int k = 0; k < 4; k++) t[k] = (1.0 - cos((2 * k + 1) * M_PI / 8.0)) / 2.0 / K;
   for (int sg = 0; sg < h2s::PQI_NSEG; sg++) {
     const double base = ldexp(1.0, h2s::PQI_OCT0 + sg / K);
     double y[4], c[4];
-    for (int k = 0; k < 4; k++) y[k] = pq_encode_d(base * (1.0 + (double)(sg % K) / K + t[k]));
+    for (int k = 0; k < 4; k++) y[k] = h2s::hd_pq_encode(base * (1.0 + (double)(sg % K) / K + t[k]));
     solve_cubic(t, y, c);
     (*out)[1 + sg] = make_float4((float)c[3], (float)c[2], (float)c[1], (float)c[0]);
   }
@@ -352,32 +352,17 @@ static void build_seg_table(const Fn& eotf, std::vector<float4>* out) {
   for (int k = 0; k < 4; k++) t[k] = (1.0 - cos((2 * k + 1) * M_PI / 8.0)) / 2.0;
   out->resize(h2s::PQ_NSEG);
   for (int i = 0; i < h2s::PQ_NSEG; i++) {
-    // solve the 4x4 Vandermonde system A c = y (c = c0..c3) by Gaussian elimination
-    double A[4][5];
-    for (int k = 0; k < 4; k++) {
-      for (int j = 0; j < 4; j++) A[k][j] = pow(t[k], j);
-      A[k][4] = eotf((i + t[k]) / h2s::PQ_SEG);
-    }
-    for (int col = 0; col < 4; col++) {
-      int piv = col;
-      for (int r = col + 1; r < 4; r++)
-        if (fabs(A[r][col]) > fabs(A[piv][col])) piv = r;
-      for (int j = 0; j < 5; j++) std::swap(A[col][j], A[piv][j]);
-      for (int r = 0; r < 4; r++) {
-        if (r == col) continue;
-        const double fct = A[r][col] / A[col][col];
-        for (int j = col; j < 5; j++) A[r][j] -= fct * A[col][j];
-      }
-    }
-    double c[4];
-    for (int k = 0; k < 4; k++) c[k] = A[k][4] / A[k][k];
+    double y[4], c[4];
+    for (int k = 0; k < 4; k++) y[k] = eotf((i + t[k]) / h2s::PQ_SEG);
+    solve_cubic(t, y, c);
     if (i == 0) c[0] = 0.0;  // E = 0 maps to exactly 0, as zimg's x > 0 test
     (*out)[i] = make_float4((float)c[3], (float)c[2], (float)c[1], (float)c[0]);
   }
 }
 
 void build_pq_table(double scale, std::vector<float4>* out) {
-  const double m1 = 2610.0 / 16384, m2 = 2523.0 / 32, c1 = 3424.0 / 4096, c2 = 2413.0 / 128, c3 = 2392.0 / 128;
+  // (hd_pq_eotf's expression with the table's own guard: past the pole, den <= 0, +inf)
+  const double m1 = h2s::PQ_M1_D, m2 = h2s::PQ_M2_D, c1 = h2s::PQ_C1_D, c2 = h2s::PQ_C2_D, c3 = h2s::PQ_C3_D;
   build_seg_table([&](double e) {
     if (!(e > 0)) return 0.0;
     const double xp = pow(e, 1.0 / m2);
@@ -449,7 +434,7 @@ void resolve_fast(const h2s_ctx* c, const KParams& k, FastParams* F) {
   F->hable_kb = (float)(0.25 / 15.0 * (double)k.hable_peak_inv);
   F->mob_j = k.mob_j, F->mob_a = k.mob_a, F->mob_b = k.mob_b, F->mob_k = k.mob_k;
   F->npl_1e4 = k.npl_1e4, F->e4_npl = k.e4_npl;
-  F->b_e1min = (float)pq_encode_d(1e-6 * p->npl / 10000.0);
+  F->b_e1min = (float)h2s::hd_pq_encode(1e-6 * p->npl / 10000.0);
   F->tw_fold = (float)(p->npl / k.t_white);
   // libplacebo branch: 255 ((x ainv)^(1/2.4) - b) as exp2(log2(x)/2.4 + k1) - k2
   F->lp_k1 = (float)(log2((double)k.enc_ainv) / 2.4 + log2(255.0));

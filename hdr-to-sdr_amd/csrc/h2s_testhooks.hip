@@ -1,10 +1,10 @@
 // h2s_testhooks.hip — private test entries (not in include/h2s.h): host arrays
 // in and out, synchronous, on the current device; 0 or a negative HIP error.
 // They reach the library through h2s_launch.h and the libm forms alone (libm_powf /
-// libm_expf over h2s_libm.h's tables live in h2s_device.h; no contraction inside)
+// libm_expf over h2s_libm.h's tables live in h2s_chain.h; no contraction inside)
 #include <vector>
 
-#include "h2s_device.h"
+#include "h2s_chain.h"
 #include "h2s_launch.h"
 
 namespace h2s {

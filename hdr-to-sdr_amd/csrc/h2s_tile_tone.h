@@ -10,8 +10,9 @@
 
 #include <type_traits>
 
-#include "h2s_device.h"
 #include "h2s_dovi.h"
+#include "h2s_math.h"
+#include "h2s_params.h"
 
 // The PQ table's first segment (E' < 1/128, below ~0.0015 nits), where the
 // EOTF ~ (E - E0)^6.28 and no cubic holds 1e-3 relative, is staged as the

@@ -1,7 +1,7 @@
 """Pure-Python restatement of glibc 2.35's powf / expf (x86-64 FMA variants)
 over their constant tables, for scripts/gen_libm_tables.py and
 tests/test_libm_tables.py.  The device forms are h2s::libm_powf /
-h2s::libm_expf in hdr-to-sdr_amd/csrc/h2s_device.h; this file checks the
+h2s::libm_expf in hdr-to-sdr_amd/csrc/h2s_chain.h; this file checks the
 tables and the evaluation order against the libm the oracle links.
 
 powf (e_powf.c): log2(x) = k + log2(c) + poly(z / c - 1) from a 16-entry
