@@ -436,7 +436,8 @@ hipError_t launch_route(const h2s_ctx* c, const KParams& k, const Route& r) {
 // the tile kernel serves: both of the reference's chains (the CPU chain, and
 // the libplacebo branch with the LUT on: k_tile<..., LP = 1>), the LUT on at
 // N <= 177 (its lattice byte offsets are formed in float32, exact for
-// multiples of 4 below 2^26 = 12 * 177^3 + margin), the default [EXT]
+// multiples of 4 below 2^26 = 12 * 177^3 + margin) with every value finite
+// and in [0, 1] (the CPU chain; the libplacebo branch: any), the default [EXT]
 // switches, 10/12-bit input and BASELINE's operators; frames with a 64-wide
 // tile and 16-byte aligned rows
 static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
@@ -452,6 +453,11 @@ static bool fast_params_ok(const h2s_ctx* c, const KParams& k) {
   // the CPU chain forms lattice byte offsets in float32 (exact to N = 177);
   // the libplacebo branch reads its 8-bit table, any N
   if (k.lut_enabled && c->lut_n > 177 && !k.rgba8) return false;
+  // the CPU chain's pre-multiplied lattice (k_build_lut_yuv) is built from clamped nodes, which
+  // equals lut3d's blend followed by swscale's clip only while no node needs the clamp: a lattice
+  // with a value outside [0, 1] (or not finite) runs on the generic kernel, which blends the raw
+  // nodes and clips afterwards, as the oracle does; the 8-bit table is built that way for any lattice
+  if (k.lut_enabled && !c->lut_unit && !k.rgba8) return false;
   if (k.lut_in16) return false;
   // BICUBIC: the tile kernel runs pass 1 frame by frame (not under dynamic peak detection)
   if (p.chroma_filter == H2S_CHROMA_BICUBIC && p.peak_detect) return false;
@@ -746,8 +752,16 @@ int h2s_set_lut(h2s_ctx* c, const float* rgb, int n) {
   DeviceGuard g(c->device);
   if (int rc = drain_launches(c)) return rc;
   const size_t cnt = (size_t)n * n * n;
-  std::vector<float4> host(cnt);
-  for (size_t i = 0; i < cnt; i++) host[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+  // zero records behind the lattice, as behind d_lut_yuv (ensure_lut_yuv): k_tile's stage-4 debug
+  // plane blends the same four corners on this copy, and a coordinate clamped to exactly N-1 names
+  // cell N-1, whose corners past the edge carry weight 0 but are read (up to 1 + N + N^2 records on)
+  const size_t all = cnt + 1 + (size_t)n + (size_t)n * n;
+  std::vector<float4> host(all, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  bool unit = true;  // (a NaN fails both comparisons)
+  for (size_t i = 0; i < cnt; i++) {
+    host[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+    for (int ch = 0; ch < 3; ch++) unit &= rgb[3 * i + ch] >= 0.0f && rgb[3 * i + ch] <= 1.0f;
+  }
   hipStream_t aux;
   if (int rc = aux_stream(c, &aux)) return rc;
   // a size change reallocates stream-ordered on the context's stream: a plain
@@ -758,10 +772,11 @@ int h2s_set_lut(h2s_ctx* c, const float* rgb, int n) {
   }
   c->lut_yuv_scale = -1.0f;
   c->lut8x_ok = false;
-  if (int rc = c->d_lut.reserve(c, cnt * sizeof(float4), "LUT device")) return rc;
-  hipError_t e = table_copy(c, c->d_lut, host.data(), cnt * sizeof(float4));
+  if (int rc = c->d_lut.reserve(c, all * sizeof(float4), "LUT device")) return rc;
+  hipError_t e = table_copy(c, c->d_lut, host.data(), all * sizeof(float4));
   if (e != hipSuccess) return hip_fail(c, e, "LUT upload");
   c->lut_n = n;
+  c->lut_unit = unit;
   return 0;
 }
 

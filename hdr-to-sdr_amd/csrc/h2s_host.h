@@ -195,6 +195,7 @@ struct h2s_ctx {
   h2s::host::Stream aux;
   h2s::host::Dev<float4> d_lut;
   int lut_n = 0;
+  bool lut_unit = false;  // every lattice value is finite and in [0, 1] (what d_lut_yuv's clamped build assumes)
   h2s::host::Dev<float> d_lut_yuv;  // lattice pre-multiplied into output code space (3 floats/point)
   float lut_yuv_scale = -1.0f;  // quantiser scale it was built for (-1 = stale)
   int lut_yuv_rgb = 0;          // 1: it holds plain R'G'B' records (libplacebo rgba8 form)

@@ -13,9 +13,12 @@
 //  * chroma upsampling on integer-valued floats (exact), the 1/4, 1/8 and
 //    depth-normalisation scales folded into the Y'CbCr->R'G'B' constants;
 //  * the 3D-LUT lattice pre-multiplied into output Y'CbCr code space
-//    (RGB->Y'CbCr is linear and the lattice lies in [0,1], so the swscale
-//    clip is a no-op and blend-then-convert == convert-then-blend); the
-//    tetrahedral blend then yields quantiser inputs directly;
+//    (RGB->Y'CbCr is linear, and the host routes the CPU chain here only
+//    while every lattice value is finite and in [0,1] -- h2s_set_lut records
+//    it, fast_params_ok tests it -- so the swscale clip is a no-op and
+//    blend-then-convert == convert-then-blend; any other lattice runs on the
+//    generic kernel, which clips the blend); the tetrahedral blend then
+//    yields quantiser inputs directly;
 //  * lattice gathers are buffer loads (32-bit offsets, one SGPR base);
 //  * eq's table sits in LDS.
 // Geometry (k_tile): a block of 256 threads walks 8 consecutive 64 x 32 luma

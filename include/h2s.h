@@ -385,7 +385,13 @@ const char *h2s_last_error(const h2s_ctx *ctx);
 /* ---- LUT (lut3d=file=..., src/utils.py:40, :212-225) --------------------
  * rgb: n^3 float triples in .cube order (red fastest, then green, then blue),
  * i.e. exactly the order tools/generate_lut.py:97-109 writes.  The context
- * keeps its own device copy. */
+ * keeps its own device copy.  2 <= n <= 256; any float values are taken, as
+ * lut3d takes them: the chain blends the nodes as given and the output clip
+ * follows the blend.  The tile kernel's CPU-chain form assumes nodes in [0, 1],
+ * so a lattice with any value outside [0, 1] or not finite (a creative or
+ * overshooting .cube) runs the CPU chain on the generic kernel, and
+ * h2s_query_path reports H2S_PATH_GENERIC; the libplacebo branch, whose 8-bit
+ * table is built with the generic arithmetic, keeps its path for any lattice. */
 int h2s_set_lut(h2s_ctx *ctx, const float *rgb, int n);
 
 /* ---- params (FFMPEG_CONVERT_FILTER.format, src/utils.py:38-42) ----------- */

@@ -61,18 +61,28 @@ def lattice(n):
     return _LAT[n]
 
 
-def lattice_max_step(n):
-    a = lattice(n).reshape(n, n, n, 3).astype(np.float64)
+def lattice_size(lat):
+    """N of a lattice given as [N^3, 3] (or [N, N, N, 3])."""
+    n = round((np.asarray(lat).size // 3) ** (1 / 3))
+    assert n ** 3 * 3 == np.asarray(lat).size, np.asarray(lat).shape
+    return n
+
+
+def lattice_max_step(n, lat=None):
+    """The largest |difference| of two nodes adjacent along an axis; lat: the
+    lattice itself ([n^3, 3]) where it is not the bundled one of size n."""
+    a = (lattice(n) if lat is None else np.asarray(lat)).reshape(n, n, n, 3).astype(np.float64)
     return max(float(np.abs(np.diff(a, axis=ax)).max()) for ax in range(3))
 
 
-def lattice_slope(n, s3):
+def lattice_slope(n, s3, lat=None):
     """Per pixel, output channel and input axis: the largest |corner
     difference| along that axis over the lattice cell that holds the stage-3
     coordinates s3 (3, H, W) in [0, 1], times (n - 1): a bound on the
     tetrahedral interpolant's partial derivatives there (it is linear on each
-    tetrahedron, with slopes equal to corner differences).  Returns (c, a, H, W)."""
-    a = lattice(n).reshape(n, n, n, 3).astype(np.float64)          # [b][g][r][c]
+    tetrahedron, with slopes equal to corner differences).  lat: the lattice
+    itself ([n^3, 3]) where it is not the bundled one.  Returns (c, a, H, W)."""
+    a = (lattice(n) if lat is None else np.asarray(lat)).reshape(n, n, n, 3).astype(np.float64)   # [b][g][r][c]
     x = np.clip(np.nan_to_num(s3, nan=0.0), 0.0, 1.0) * (n - 1)
     i = np.minimum(np.floor(x).astype(np.int64), n - 2)
     ir, ig, ib = i[0], i[1], i[2]
@@ -113,16 +123,23 @@ def tone_uncertainty(params, op):
 
 
 class Planes:
-    """The oracle's float planes of one frame (stages 1..5, computed on demand)."""
+    """The oracle's float planes of one frame (stages 1..5, computed on demand).
+    lat: the lattice the chain runs on ([N^3, 3]; lut_n is then its N), where
+    it is not the bundled one of size lut_n; the tolerances that depend on the
+    lattice (float_tolerance, lp_gate) read it from here."""
 
-    def __init__(self, params, buf, W, H, lut_n=65, avg_pq=0.0):
+    def __init__(self, params, buf, W, H, lut_n=65, avg_pq=0.0, lat=None):
+        self.lat_given = lat is not None
+        if lat is not None:
+            lut_n = lattice_size(lat)
+        self.lat = lattice(lut_n) if lat is None else np.ascontiguousarray(lat, dtype=np.float32).reshape(-1, 3)
         self.params, self.buf, self.W, self.H, self.lut_n, self.avg_pq = params, buf, W, H, lut_n, avg_pq
         self.op = oracle.params_from(params.to_c())
         self._p = {}
 
     def __getitem__(self, stage):
         if stage not in self._p:
-            self._p[stage] = oracle.debug_float(self.op, lattice(self.lut_n), self.buf, self.W, self.H,
+            self._p[stage] = oracle.debug_float(self.op, self.lat, self.buf, self.W, self.H,
                                                 stage, avg_pq=self.avg_pq).astype(np.float64)
         return self._p[stage]
 
@@ -142,7 +159,7 @@ def _stage2_spread(params, P, U1, lin=None):
     lin: the stage-1 values to take it at (any (3, ...) subset of P[1])."""
     lin = np.nan_to_num(P[1] if lin is None else lin, nan=0.0, posinf=0.0).astype(np.float64)
     out = np.zeros(lin.shape)
-    lat = lattice(P.lut_n) if params.lut_enabled else None
+    lat = P.lat if params.lut_enabled else None
     for k in range(3):
         h = np.maximum(1e-3 * np.abs(lin[k]), 1e-9)
         hi, lo = lin.copy(), lin.copy()
@@ -205,7 +222,9 @@ def lp_stage3_bound(params, kernel, P, ys, xs):
 
 def float_tolerance(params, kernel, stage, kind, P):
     """Per-value tolerance of the (kernel, stage) float check on the oracle's
-    planes P (a Planes); pure: depends on the oracle only.  tol = 1e-3
+    planes P (a Planes; the lattice, its slope and its k8 bound are P's, so
+    Planes(..., lat=) judges another lattice than the bundled one); pure:
+    depends on the oracle only.  tol = 1e-3
     relative + U, U the uncertainty the chain's own conditioning puts on the
     stage (stage 1: the EOTF's kappa, and k_tile's first-segment table floor;
     carried stage to stage by the Jacobian of the tone map, the derivative of
@@ -267,7 +286,7 @@ def float_tolerance(params, kernel, stage, kind, P):
                 return np.maximum(x, 0.0) ** (1 / 2.4)
             U = 0.5 * (g(w2 + U) - g(w2 - U))
     if stage >= 4 and not lp and params.lut_enabled:   # the tetrahedral interpolant's local slope
-        U = np.einsum('cahw,ahw->chw', lattice_slope(P.lut_n, P[3]), U + 1e-5)
+        U = np.einsum('cahw,ahw->chw', lattice_slope(P.lut_n, P[3], P.lat), U + 1e-5)
     if lp and params.lut_enabled and stage >= 4:
         # after the 8-bit download the values are exact functions of the
         # download codes: equal codes give equal values (float noise), a code
@@ -286,7 +305,10 @@ def float_tolerance(params, kernel, stage, kind, P):
         x = np.clip(np.nan_to_num(P[3]), 0.0, 1.0) * qs + qo + 0.5
         dist = np.abs(x - np.round(x))
         T.near_tie = (dist < TIE_WINDOW).any(axis=0)
-        k8 = math.ceil(lattice_max_step(65) * 64) + 1
+        # (the bundled lattices share the 65^3 one's bound; a lattice handed to
+        # Planes is judged by its own steepest step)
+        k8 = math.ceil(lattice_max_step(P.lut_n, P.lat) * (P.lut_n - 1) if P.lat_given
+                       else lattice_max_step(65) * 64) + 1
         T.flip_lim = k8 / 255.0 if stage == 4 else 224 * (1 << (q - 8)) * k8 / 255.0 + 1.0
     T.want, T.tol, T.rel, T.floor, T.keep, T.skip, T.seg0 = want, tol, rel, floor, keep, skip, seg0
     T.kappa, T.U = kappa, U

@@ -93,11 +93,15 @@ def attribute(params, kernel, got, want, src, W, H, lut_n=65, lattice=None, knee
     dynamic peak detection, each frame's (peak, average PQ) as
     oracle.process_dynamic(knees=...) reports them.  Returns a report:
     samples, beyond, attributed, unattributed (counts), max_steps, k8_steps,
-    near_tie_px (pixels examined that had a channel within the bound)."""
-    from float_gate import lattice as _lat
+    near_tie_px (pixels examined that had a channel within the bound).
+    lattice: the lattice in force ([N^3, 3]; lut_n is then its N) where it is
+    not the bundled one of size lut_n; k8 and the planes are that lattice's."""
+    from float_gate import lattice as _lat, lattice_size
+    if lattice is not None:
+        lut_n = lattice_size(lattice)
     lat = _lat(lut_n) if lattice is None else lattice
     by, bc, step = beyond_samples(params, got, want, W, H)
-    k8 = math.ceil(lattice_max_step(lut_n) * (lut_n - 1)) + 1
+    k8 = math.ceil(lattice_max_step(lut_n, lattice) * (lut_n - 1)) + 1
     op = oracle.params_from(params.to_c())
     q = oracle.quant_bits(op)
     rep = dict(samples=int(got.size), beyond=int(by.sum() + bc.sum()), attributed=0, unattributed=0,
@@ -115,7 +119,7 @@ def attribute(params, kernel, got, want, src, W, H, lut_n=65, lattice=None, knee
         if knees is not None:      # this frame's detected peak and knee, as static parameters
             pf, avg = params.with_(peak=knees[f][0], peak_detect=False), knees[f][1]
         opf = oracle.params_from(pf.to_c())
-        P = Planes(pf, one, W, H, lut_n, avg_pq=avg)
+        P = Planes(pf, one, W, H, lut_n, avg_pq=avg, lat=lattice)
         xq = oracle.lp_download(opf, lat, one, W, H, avg_pq=avg)  # [3, H, W] exact pre-rounding values
         need = by[f] | _support(params, bc[f], W, H)
         ys, xs = np.nonzero(need)
@@ -142,9 +146,9 @@ def attribute(params, kernel, got, want, src, W, H, lut_n=65, lattice=None, knee
     return rep
 
 
-def check(params, kernel, got, want, src, W, H, lut_n=65, max_attributed_frac=3e-3, knees=None):
-    """The gate as failures (empty list = pass)."""
-    rep = attribute(params, kernel, got, want, src, W, H, lut_n, knees=knees)
+def check(params, kernel, got, want, src, W, H, lut_n=65, max_attributed_frac=3e-3, knees=None, lattice=None):
+    """The gate as failures (empty list = pass).  lattice: as attribute's."""
+    rep = attribute(params, kernel, got, want, src, W, H, lut_n, lattice=lattice, knees=knees)
     fails = []
     if rep['unattributed']:
         fails.append(f"{rep['unattributed']} samples beyond one step with no download channel within the "

@@ -35,18 +35,21 @@ def tm():
     t.close()
 
 
-def run_both(tm, params, kind, W, H, nframes=2, lut_n=65, seed=11):
+def run_both(tm, params, kind, W, H, nframes=2, lut_n=65, seed=11, lat=None):
+    """lat: the lattice ([N^3, 3]) where it is not the bundled one of size lut_n."""
     import torch
+    if lat is None:
+        lat = lattice(lut_n)
     src_cpu = synth_frames(kind, nframes, W, H, params.bits_in, device='cpu', seed=seed)
     src = src_cpu.to_torch('cuda')
     tm.set_params(params)
     if params.lut_enabled:
-        tm.set_lut(lattice(lut_n))
+        tm.set_lut(lat)
     dst = hdr2sdr.FrameBatch.empty_torch(nframes, W, H, params.bits_out, 'cuda')
     tm.process(src, dst)
     torch.cuda.synchronize()
     got = dst.to_numpy().buf.astype(np.int64)
-    want = oracle.process(oracle.params_from(params.to_c()), lattice(lut_n) if params.lut_enabled else None,
+    want = oracle.process(oracle.params_from(params.to_c()), lat if params.lut_enabled else None,
                           src_cpu.to_numpy().buf, W, H).astype(np.int64)
     return got, want, (W, H, src_cpu.to_numpy().buf)
 
@@ -87,7 +90,8 @@ def parity_report(params, got, want, W, H, q, luma_within=None, attribution=None
     return rec
 
 
-def assert_close_int(params, got, want, W, H, src=None, max_frac=5e-3, lut_n=65, kernel='k_tile', knees=None):
+def assert_close_int(params, got, want, W, H, src=None, max_frac=5e-3, lut_n=65, kernel='k_tile', knees=None,
+                     lat=None):
     """Chroma: |diff| <= one quantisation step.  Luma: eq runs after the
     quantiser, so the bound is +-1 step *before* eq: got must lie between
     eq[q-1] and eq[q+1] where eq[q] == want (eq is monotonic).
@@ -102,14 +106,16 @@ def assert_close_int(params, got, want, W, H, src=None, max_frac=5e-3, lut_n=65,
     kernel's), 'exact' (H2S_OPT_LP_EXACT or the generic kernel alone: double
     arithmetic, so in effect none) -- and none may be unattributed.  src: the
     input frames (host numpy) the attribution recomputes; knees: per-frame
-    (peak, average) under dynamic peak detection."""
+    (peak, average) under dynamic peak detection; lat: the lattice in force
+    ([N^3, 3]) where it is not the bundled one of size lut_n (the branch's k8
+    bound and the attribution's planes are that lattice's)."""
     op = oracle.params_from(params.to_c())
     q = oracle.quant_bits(op)
     if params.resolved_pipeline() == 'libplacebo' and params.lut_enabled:
         import lp_gate
         if src is None:
             raise TypeError('assert_close_int: the libplacebo branch\'s gate needs the input frames (src)')
-        rep, fails = lp_gate.check(params, kernel, got, want, src, W, H, lut_n, knees=knees)
+        rep, fails = lp_gate.check(params, kernel, got, want, src, W, H, lut_n, knees=knees, lattice=lat)
         rep['kernel'] = kernel
         parity_report(params, got, want, W, H, q, attribution=rep)
         assert not fails, '; '.join(fails)
@@ -269,16 +275,28 @@ def _morton_to_linear():
     return r | (g << 8) | (b << 16)
 
 
-@pytest.mark.parametrize('lut_n', [2, 33, 65, 177, 256])
+def _lut8x_lattice(which):
+    """A bundled lattice by size, or one of tests/lattices_ref.py's by name."""
+    if isinstance(which, int):
+        return lattice(which)
+    import lattices_ref as LR
+    return {'bumpy17': lambda: LR.bumpy(17), 'overshoot17': lambda: LR.overshoot(17, 1.15),
+            'random2': lambda: LR.random_unit(2), 'random3': lambda: LR.random_unit(3)}[which]()
+
+
+@pytest.mark.parametrize('lut_n', [2, 33, 65, 177, 256, 'bumpy17', 'overshoot17', 'random2', 'random3'])
 def test_lut8x_table_equals_the_oracle_lut3d_8bit(lut_n):
     """The libplacebo branch's lut3d table (k_build_lut8x, through the
     private entry h2stest_lut8x) equals the oracle's lut3d 8-bit path for
-    every one of the 2^24 rgba8 code triples, bit for bit."""
+    every one of the 2^24 rgba8 code triples, bit for bit: on the bundled
+    lattices, a rough one, one with nodes outside [0, 1] (truncated, then
+    clipped to the 8-bit range) and the two smallest sizes with random nodes."""
     from hdr2sdr import _abi
     L = ctypes.CDLL(_abi.LIB_PATH)
     L.h2stest_lut8x.restype = ctypes.c_int
     L.h2stest_lut8x.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lat = np.ascontiguousarray(lattice(lut_n), dtype=np.float32)
+    lat = np.ascontiguousarray(_lut8x_lattice(lut_n), dtype=np.float32)
+    lut_n = round(lat.shape[0] ** (1 / 3))
     got = np.empty(1 << 24, dtype=np.uint32)
     assert L.h2stest_lut8x(lat.ctypes.data, lut_n, got.ctypes.data) == 0
     want = oracle.lut8x_table(lat)[_morton_to_linear()]
@@ -300,15 +318,16 @@ def test_lut8x_table_rebuilt_after_set_lut(tm):
 # tile path) and the generic kernel (FAST_PATH 0).  The gate itself (what is
 # allowed beyond 1e-3 and why) is tests/float_gate.py, shared with the CPU
 # mutation tests of tests/test_float_gate.py that show it rejects real errors.
-def check_float_stage(tm, kernel, cfg, kind, stage, W=128, H=64):
-    """One (kernel, config, content, stage) float check; returns its report."""
+def check_float_stage(tm, kernel, cfg, kind, stage, W=128, H=64, lat=None):
+    """One (kernel, config, content, stage) float check; returns its report.
+    lat: the lattice ([N^3, 3]) where it is not the bundled 65^3 one."""
     import json
     import os
     from hdr2sdr import _abi
     params = hdr2sdr.TonemapParams(**FLOAT_CFGS[cfg])
     src = synth_frames(kind, 1, W, H, params.bits_in, device='cpu', seed=3)
     tm.set_params(params)
-    tm.set_lut(lattice(65))
+    tm.set_lut(lattice(65) if lat is None else lat)
     tm.set_option(_abi.OPT_FAST_PATH, 1 if kernel == 'k_tile' else 0)
     try:
         dsrc = src.to_torch('cuda')
@@ -317,7 +336,7 @@ def check_float_stage(tm, kernel, cfg, kind, stage, W=128, H=64):
         got = tm.debug_float(dsrc, stage)
     finally:
         tm.set_option(_abi.OPT_FAST_PATH, 1)
-    T = float_tolerance(params, kernel, stage, kind, Planes(params, src.to_numpy().buf, W, H))
+    T = float_tolerance(params, kernel, stage, kind, Planes(params, src.to_numpy().buf, W, H, lat=lat))
     report, fails = judge_float(params, kernel, kind, stage, got, T)
     report['cfg'] = cfg
     if os.environ.get('H2S_FLOAT_REPORT'):

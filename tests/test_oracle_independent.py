@@ -94,13 +94,18 @@ def curve(tm, x, peak=10.0):
     return np.where(x <= j, x, (b * b + 2.0 * b * j + j * j) / (b - a) * (x + a) / (x + b))
 
 
-def tetrahedral(lat, s):
-    """lut3d tetrahedral at lattice coordinates s (..., 3) in [0, N-1]: walk
-    from the cell's low corner along the axes in decreasing fraction order."""
+def tetrahedral(lat, s, walk=(0, 1, 2)):
+    """lut3d tetrahedral at lattice coordinates s (..., 3) in [0, N-1], on the
+    lattice lat [b][g][r][c] (any values; nothing is clipped here): walk
+    from the cell's low corner along the axes in decreasing fraction order.
+    walk: the order the sorted axes are taken in; anything but (0, 1, 2) is a
+    deliberately wrong tetrahedron of the same cell (tests/lattices_ref.py's
+    mutants): its affine interpolant evaluated at s, which on a cell the
+    lattice is affine over equals the right one."""
     n = lat.shape[0]
     base = np.minimum(np.floor(s), n - 2).astype(np.int64)
     d = s - base
-    order = np.argsort(-d, axis=-1, kind='stable')
+    order = np.argsort(-d, axis=-1, kind='stable')[..., list(walk)]
     ds = np.take_along_axis(d, order, axis=-1)
     w = np.stack([1.0 - ds[..., 0], ds[..., 0] - ds[..., 1], ds[..., 1] - ds[..., 2], ds[..., 2]], -1)
     out = np.zeros(s.shape)
@@ -136,10 +141,15 @@ def m2020_709():
     return np.linalg.solve(m709, m2020)
 
 
-def chain(y, u, v, bits_in, bits_out, hlg, tm, gamma, lut_n, native=False, luma_w=(1.0, 1.0, 1.0)):
+def chain(y, u, v, bits_in, bits_out, hlg, tm, gamma, lut_n, native=False, luma_w=(1.0, 1.0, 1.0), lat=None,
+          tetra=tetrahedral):
     """One frame (planes as integer arrays) -> output planes.  lut_n = 0: the
     LUT off (linear BT.2020 -> BT.709 matrix, BT.1886 encode, clip); native:
-    quantise at the output depth (compat8 quantises at 8 bits, then shifts)."""
+    quantise at the output depth (compat8 quantises at 8 bits, then shifts).
+    lat: the lattice [b][g][r][c] (default: the bundled one of size lut_n);
+    tetra: the interpolation (tests/lattices_ref.py passes its mutants)."""
+    if lut_n and lat is None:
+        lat = lattice(lut_n)
     s = 1 << (bits_in - 8)
     Y = (y.astype(np.float64) - 16 * s) / (219 * s)
     Cb = upsample((u.astype(np.float64) - 128 * s) / (224 * s))
@@ -161,7 +171,7 @@ def chain(y, u, v, bits_in, bits_out, hlg, tm, gamma, lut_n, native=False, luma_
     L = L * (curve(tm, sig) / sig)[..., None]
     if lut_n:
         G = np.power(np.maximum(L, 0.0), 1.0 / 2.4)
-        rgb = np.clip(tetrahedral(lattice(lut_n), np.clip(G * (lut_n - 1), 0, lut_n - 1)), 0.0, 1.0)
+        rgb = np.clip(tetra(lat, np.clip(G * (lut_n - 1), 0, lut_n - 1)), 0.0, 1.0)
     else:
         rgb = np.clip(np.power(np.maximum(L @ m2020_709().T, 0.0), 1.0 / 2.4), 0.0, 1.0)
     Yo = rgb @ np.array([0.2126, 0.7152, 0.0722])
@@ -238,11 +248,14 @@ def rgb_to_lms():
     return hpe @ rgb_to_xyz([(0.708, 0.292), (0.170, 0.797), (0.131, 0.046)])
 
 
-def chain_lp(y, u, v, bits_out, lut_n, white=203.0, ipt=False, bits_in=10, hlg=False):
+def chain_lp(y, u, v, bits_out, lut_n, white=203.0, ipt=False, bits_in=10, hlg=False, lat=None):
     """PQ 10-bit in; tone curve on max(R,G,B) (or on the intensity of IPT-PQ,
     P and T kept: L'M'S' += I' - I); BT.1886 encode against the
     target black; 8-bit rgba download; lut3d's 8-bit path (truncating);
-    BT.709 limited-range Y'CbCr at the output depth, no eq (gamma 1)"""
+    BT.709 limited-range Y'CbCr at the output depth, no eq (gamma 1).  lat: the
+    lattice [b][g][r][c] (default: the bundled one of size lut_n)"""
+    if lat is None:
+        lat = lattice(lut_n)
     s = 1 << (bits_in - 8)
     Y = (y.astype(np.float64) - 16 * s) / (219 * s)
     Cb = upsample((u.astype(np.float64) - 128 * s) / (224 * s))
@@ -270,7 +283,7 @@ def chain_lp(y, u, v, bits_out, lut_n, white=203.0, ipt=False, bits_in=10, hlg=F
     lb = (1.0 / 1000.0) ** (1 / 2.4)
     enc = np.power(np.maximum(T, 0.0) / (1 - lb) ** 2.4, 1 / 2.4) - lb / (1 - lb)
     q8 = np.floor(np.clip(enc, 0.0, 1.0) * 255.0 + 0.5)
-    o = tetrahedral(lattice(lut_n), q8 / 255.0 * (lut_n - 1))
+    o = tetrahedral(lat, q8 / 255.0 * (lut_n - 1))
     rgb = np.clip(np.floor(o * 255.0), 0, 255) / 255.0
     Yo = rgb @ np.array([0.2126, 0.7152, 0.0722])
     cb = (rgb[..., 2] - Yo) / 1.8556
