@@ -213,7 +213,7 @@ int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const c
 }
 
 // record that this context queued work on stream s (after the launches)
-static int note_launch(h2s_ctx* c, hipStream_t s) {
+int note_launch(h2s_ctx* c, hipStream_t s) {
   if (c->pend.size() >= 32) {   // recycle the events that have completed
     size_t j = 0;
     for (size_t i = 0; i < c->pend.size(); i++) {
@@ -903,6 +903,10 @@ int h2s_set_option(h2s_ctx* c, int key, int64_t value) {
     case H2S_OPT_TEST_PEAK_BLOCKS:
       if (value < 1 || value > h2s::PEAK_BLOCKS_MAX) return fail(c, H2S_E_INVALID_ARG, "peak blocks must be in [1, 256]");
       c->peak_blocks = (int)value;
+      return 0;
+    case H2S_OPT_TEST_SCALE_UPLOADS:
+      if (value != c->scale_taps.uploads)
+        return fail(c, H2S_E_INVALID_ARG, "scaled-output tap uploads: " + std::to_string(c->scale_taps.uploads));
       return 0;
     case H2S_OPT_TEST_PEAK_CHUNK:
       if (value < 0 || value > 4096) return fail(c, H2S_E_INVALID_ARG, "peak chunk must be in [0, 4096]");

@@ -7,6 +7,7 @@
 //   h2s_api_peak.hip     the dynamic peak's host side
 //   h2s_api_preview.hip  the two preview panes
 //   h2s_api_dovi.hip     Dolby Vision profile 5: the records' validation and upload
+//   h2s_api_scale.hip    the scaled 4:2:0 output (h2s_process_scaled)
 //
 // Everything declared here has hidden visibility: the library's dynamic
 // symbols are the h2s_* calls of include/h2s.h and nothing else.
@@ -178,6 +179,24 @@ struct Ordered {
   }
 };
 
+// the tap tables of the scaled output (resize_taps), cached for one
+// (W, H) -> (ow, oh): four axes (luma x, y; chroma x, y), the weights in one
+// device array and the first taps in another, uploaded once.  The host copies
+// stay: the launch's rows per block are picked from the first taps
+struct ScaleTaps {
+  enum Axis { X, Y, CX, CY };
+  int W = 0, H = 0, ow = 0, oh = 0;   // the key (0: none yet)
+  int T[4] = {0, 0, 0, 0};
+  size_t woff[4] = {0, 0, 0, 0}, soff[4] = {0, 0, 0, 0};
+  std::vector<float> w;
+  std::vector<int> s;
+  Dev<float> d_w;
+  Dev<int> d_s;
+  long long uploads = 0;   // (H2S_OPT_TEST_SCALE_UPLOADS)
+  const float* wt(int a) const { return d_w + woff[a]; }
+  const int* st(int a) const { return d_s + soff[a]; }
+};
+
 }  // namespace host
 }  // namespace h2s
 
@@ -255,6 +274,11 @@ struct h2s_ctx {
   std::vector<h2s::host::Event> pend, ev_free;
   h2s::host::Dev<float2> d_chr;             // BICUBIC chroma: one frame's per-pixel (Cb, Cr)
   h2s::host::Ordered chr_use;               // after the last BICUBIC two-pass launch (d_chr in use)
+  // scaled output (h2s_process_scaled): the chain's full-size planar frames of
+  // one chunk, then a host output's staging; the cached tap tables
+  h2s::host::Dev<uint8_t> d_scale;
+  h2s::host::ScaleTaps scale_taps;
+  h2s::host::Ordered scale_use;             // after the last scaled call (d_scale and the tables in use)
 };
 
 namespace h2s {
@@ -349,6 +373,7 @@ void timing_end(h2s_ctx* c, hipStream_t s);
 int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
                    Format in_fmt, Format out_fmt, int dovi_f0 = 0);
 int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what);
+int note_launch(h2s_ctx* c, hipStream_t s);
 
 // ---- h2s_api_dovi.hip ----
 

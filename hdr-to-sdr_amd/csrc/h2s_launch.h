@@ -1,6 +1,6 @@
 // h2s_launch.h — the one declaration of every host-callable kernel launcher.
 // Included by the unit that defines a launcher (h2s_kernels.hip, h2s_peak.hip,
-// h2s_fast.hip, h2s_preview.hip) and by every unit that calls one (the host
+// h2s_fast.hip, h2s_preview.hip, h2s_scale.hip) and by every unit that calls one (the host
 // units, h2s_testhooks.hip), so a signature or an
 // enum value that drifts apart is a compile error, not a misrouted launch.
 #pragma once
@@ -17,6 +17,7 @@ struct PeakModel;         // h2s_peak.h
 struct PeakState;
 struct PeakTail;
 struct SrcPreviewParams;  // h2s_srcprev.h
+struct ScaleParams;       // h2s_scale.h
 
 // launch_process's form: PF_VEC the rows allow vector accesses, PF_OUT8 8-bit
 // output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma into P.chr444)
@@ -52,5 +53,8 @@ hipError_t launch_yuv8_rgb24(const uint8_t* yp, long long yls, const uint8_t* up
                              long long yuv_fp, int w, int h, uint8_t* rgb, long long rls, long long rgb_fp,
                              const uint8_t* glut, int nframes, hipStream_t s);
 hipError_t launch_source_rgb24(const SrcPreviewParams& P, int nframes, hipStream_t s);
+
+// h2s_scale.hip: every plane of nframes frames in one launch (src_bps: bytes of a scratch sample)
+hipError_t launch_scale420(const ScaleParams& P, int src_bps, int nframes, hipStream_t s);
 
 }  // namespace h2s

@@ -11,7 +11,7 @@ from .dovi import DoviCurve, DoviRpu  # noqa: F401
 from .engine import Tonemapper  # noqa: F401
 from .frames import FrameBatch, frame_bytes  # noqa: F401
 from .lut import LUT_SIZE, cube_text, generate_cube_lines, generate_lattice, load_cube, parse_cube  # noqa: F401
-from .plan import H2SProcess, PipePlan, plan_from_argv  # noqa: F401
+from .plan import H2SProcess, PipePlan, plan_from_argv, scaled_size  # noqa: F401
 from .preview import PREVIEW_SIZE, Previewer, fit_size, source_box  # noqa: F401
 
 __all__ = [
@@ -19,5 +19,5 @@ __all__ = [
     'is_gpu_only_tonemapper', 'parse_filter_chain', 'Tonemapper', 'FrameBatch',
     'frame_bytes', 'LUT_SIZE', 'cube_text', 'generate_cube_lines', 'generate_lattice',
     'load_cube', 'parse_cube', 'H2SError', 'lib', 'H2SProcess', 'PipePlan', 'plan_from_argv',
-    'PREVIEW_SIZE', 'Previewer', 'fit_size', 'source_box', 'DoviCurve', 'DoviRpu',
+    'PREVIEW_SIZE', 'Previewer', 'fit_size', 'source_box', 'DoviCurve', 'DoviRpu', 'scaled_size',
 ]

@@ -57,6 +57,7 @@ OPT_TEST_FAIL_AFTER_LAUNCH = 0x7f000000 + 1
 OPT_RESERVED_PRIVATE_2 = 0x7f000000 + 2   # was OPT_TEST_PEAK_FORM: now INVALID_ARG
 OPT_TEST_PEAK_CHUNK = 0x7f000000 + 3
 OPT_TEST_PEAK_BLOCKS = 0x7f000000 + 4
+OPT_TEST_SCALE_UPLOADS = 0x7f000000 + 5   # a query: OK when the scaled output's tap uploads equal the value
 PATH_TILE, PATH_TILE_TAIL, PATH_GENERIC, PATH_TWO_PASS = 1, 2, 3, 4
 ABI_VERSION = 3
 ABI_MINOR = 4   # include/h2s.h H2S_ABI_MINOR (the loaded library may be newer, not older)
@@ -70,6 +71,7 @@ EXPORTS = (
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
     'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch', 'h2s_set_dovi',
+    'h2s_scaled_size', 'h2s_process_scaled',
 )
 
 
@@ -213,6 +215,10 @@ def lib() -> ctypes.CDLL:
                                                           ctypes.c_int, ctypes.c_void_p]),
         # (rpu: an array of dovi.H2SDoviRpu, or None)
         'h2s_set_dovi': (ctypes.c_int, [c_ctx, ctypes.c_void_p, ctypes.c_int]),
+        'h2s_scaled_size': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+        'h2s_process_scaled': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SFrames),
+                                              ctypes.c_int, ctypes.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

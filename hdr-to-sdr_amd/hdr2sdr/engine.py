@@ -183,15 +183,35 @@ class Tonemapper:
         self._check(self._L.h2s_process(self._ctx, ctypes.byref(di), ctypes.byref(do), int(n),
                                         self._stream_ptr(stream)))
 
-    def __call__(self, src: FrameBatch, stream: Any = None, out_layout: str = 'planar') -> FrameBatch:
+    def process_scaled(self, src: FrameBatch, dst: FrameBatch, stream: Any = None,
+                       nframes: 'int | None' = None) -> None:
+        """Tone-map src and resize it to dst's width x height in one call
+        (h2s_process_scaled: the chain's quantised 4:2:0 output through a
+        trailing bicubic ``scale=``; asynchronous when both batches are on the
+        device).  With dst of src's size this is ``process``."""
+        n = src.nframes if nframes is None else nframes
+        if n > src.nframes or n > dst.nframes:
+            raise ValueError(f'nframes {n} exceeds the batch ({src.nframes} in, {dst.nframes} out)')
+        self._use_layouts(src, dst)
+        di, do = src.descriptor(), dst.descriptor()
+        self._check(self._L.h2s_process_scaled(self._ctx, ctypes.byref(di), ctypes.byref(do), int(n),
+                                               self._stream_ptr(stream)))
+
+    def __call__(self, src: FrameBatch, stream: Any = None, out_layout: str = 'planar',
+                 size: 'tuple[int, int] | None' = None) -> FrameBatch:
+        """The converted batch, allocated beside src in ``out_layout``; with
+        ``size=(w, h)`` at that size (process_scaled)."""
         if self.params is None:
             raise ValueError('set_params first')
+        w, h = (src.width, src.height) if size is None else (int(size[0]), int(size[1]))
         if src.is_torch:
-            dst = FrameBatch.empty_torch(src.nframes, src.width, src.height, self.params.bits_out,
-                                         src.buf.device, out_layout)
+            dst = FrameBatch.empty_torch(src.nframes, w, h, self.params.bits_out, src.buf.device, out_layout)
         else:
-            dst = FrameBatch.empty_numpy(src.nframes, src.width, src.height, self.params.bits_out, out_layout)
-        self.process(src, dst, stream)
+            dst = FrameBatch.empty_numpy(src.nframes, w, h, self.params.bits_out, out_layout)
+        if size is None:
+            self.process(src, dst, stream)
+        else:
+            self.process_scaled(src, dst, stream)
         return dst
 
     def set_option(self, key: int, value: int) -> None:

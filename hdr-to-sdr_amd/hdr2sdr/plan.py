@@ -15,7 +15,8 @@ encode and mux. The tone-map chain moves onto the GPU between two pipes:
              ``in_subsampling``; the source's own family either way, so a
              full-range or top-left source's codes cross the pipe untouched and
              the kernels honour the tags, ``in_range`` / ``in_chroma_location``)
-    libh2s:  h2s_process() on batches of frames
+    libh2s:  h2s_process() on batches of frames (h2s_process_scaled() when the
+             plan asks for a smaller deliverable, ``scale=``)
     encode:  ffmpeg -f rawvideo … -i - -i IN <every non-filter option build() chose>
 
 ``plan_from_argv`` takes the argv the reference's own ``build()`` produced.
@@ -58,6 +59,21 @@ SOURCE_CHROMA_LOCATION = {'': 'left', 'unknown': 'left', 'unspecified': 'left', 
 TRANSFERS = {'smpte2084': 'smpte2084', 'arib-std-b67': 'arib-std-b67', '': 'smpte2084'}
 
 
+def scaled_size(in_w: int, in_h: int, box_w: int, box_h: int) -> Tuple[int, int]:
+    """The size of a scaled 4:2:0 deliverable (h2s_scaled_size, which this
+    restates so that planning needs no library): the aspect fit of
+    ``scale=box_w:box_h:force_original_aspect_ratio=decrease`` (libavfilter
+    scale_eval: av_rescale, then min with the box), each dimension then rounded
+    down to even and not below 2 (``force_divisible_by=2``)."""
+    in_w, in_h, box_w, box_h = int(in_w), int(in_h), int(box_w), int(box_h)
+    if min(in_w, in_h, box_w, box_h) <= 0:
+        raise ValueError('scaled sizes must be positive')
+    tw = (box_h * in_w + in_h // 2) // in_h
+    th = (box_w * in_h + in_w // 2) // in_w
+    w, h = max(min(tw, box_w), 1), max(min(th, box_h), 1)
+    return max(w & ~1, 2), max(h & ~1, 2)
+
+
 @dataclass
 class PipePlan:
     decode: 'list[str]'
@@ -81,6 +97,19 @@ class PipePlan:
     # Dolby Vision profile 5: a DoviRpu for every frame, or a callable
     # dovi(first_frame, count) -> list[DoviRpu]; None: not such a source
     dovi: Any = None
+    # the deliverable's size (``scale=``); None: the source's
+    out_width: 'int | None' = None
+    out_height: 'int | None' = None
+
+    def __post_init__(self):
+        if self.out_width is None:
+            self.out_width = self.width
+        if self.out_height is None:
+            self.out_height = self.height
+
+    @property
+    def scaled(self) -> bool:
+        return (self.out_width, self.out_height) != (self.width, self.height)
 
     @property
     def frame_bytes_in(self) -> int:
@@ -89,7 +118,7 @@ class PipePlan:
 
     @property
     def frame_bytes_out(self) -> int:
-        return self.width * self.height * 3 // 2 * (1 if self.params.bits_out == 8 else 2)
+        return self.out_width * self.out_height * 3 // 2 * (1 if self.params.bits_out == 8 else 2)
 
 
 def _remap_input(spec: str) -> str:
@@ -102,7 +131,8 @@ def _remap_input(spec: str) -> str:
 def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[str, Any] | None' = None,
                    mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar',
                    in_subsampling: str = '420', in_range: str = 'tv',
-                   in_chroma_location: str = 'left', dovi: Any = None) -> PipePlan:
+                   in_chroma_location: str = 'left', dovi: Any = None,
+                   scale: 'Tuple[int, int] | None' = None) -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
 
     in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
@@ -152,6 +182,13 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     (src/ffmpeg_command.py:96-144); any other chain raises ValueError.  The
     unspecified ``color_transfer`` such streams carry is not an error: the
     kernels ignore the transfer once records are set.
+
+    scale: None, or the (box_w, box_h) box of a smaller deliverable (a 4K
+    master as 1080p: ``scale=(1920, 1080)``).  The out size is ``scaled_size``
+    of the source in that box; the encode pipe carries frames of that size
+    (``-s``, ``frame_bytes_out``) and the run loop converts and resizes each
+    batch in one call (``Tonemapper.process_scaled``), with no second pass on
+    the CPU.  With None every argv and every byte is as without the argument.
 
     Raises ValueError for an argv without a tone-map filter graph, and for a
     Dolby Vision profile 5 source without ``dovi`` (its RPU cannot cross the
@@ -256,12 +293,14 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     pipe_out = (PIPE_PIX_FMT_SEMI if out_layout == 'semi' else PIPE_PIX_FMT)[bits_out]
     decode = [exe, '-loglevel', 'error', '-nostdin', '-i', input_path, '-map', '0:v:0',
               '-f', 'rawvideo', '-pix_fmt', pipe_in, '-']
-    encode = [exe, '-loglevel', 'info', '-f', 'rawvideo', '-pix_fmt', pipe_out, '-s', f'{W}x{H}',
+    OW, OH = (W, H) if scale is None else scaled_size(W, H, scale[0], scale[1])
+    encode = [exe, '-loglevel', 'info', '-f', 'rawvideo', '-pix_fmt', pipe_out, '-s', f'{OW}x{OH}',
               '-r', fps, '-i', '-', '-i', input_path, '-map', '0:v:0'] + encode_opts
     return PipePlan(decode=decode, encode=encode, params=params, lut_path=lut_path, width=W, height=H,
                     input_path=input_path, output_path=output_path, reference_argv=argv,
                     in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling,
-                    in_range=in_range, in_chroma_location=in_chroma_location, dovi=dovi)
+                    in_range=in_range, in_chroma_location=in_chroma_location, dovi=dovi,
+                    out_width=OW, out_height=OH)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -301,7 +340,7 @@ class H2SProcess:
         self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout,
                                              plan.in_subsampling, plan.in_range, plan.in_chroma_location)
                      for _ in range(max(1, int(depth)))]
-        self._dst = FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_out, plan.layout)
+        self._dst = FrameBatch.empty_pinned(self._batch, plan.out_width, plan.out_height, p.bits_out, plan.layout)
         self._free: 'queue.Queue[Optional[int]]' = queue.Queue()
         self._filled: 'queue.Queue[Optional[Tuple[int, int]]]' = queue.Queue()
         for i in range(len(self._src)):
@@ -354,7 +393,10 @@ class H2SProcess:
                 if self.plan.dovi is not None:   # this batch's records (frames self.frames .. + n)
                     from .dovi import resolve_records
                     self._tm.set_dovi(resolve_records(self.plan.dovi, self.frames, n))
-                self._tm.process(self._src[slot], self._dst, nframes=n)   # synchronous for host frames
+                if self.plan.scaled:             # convert and resize in one call
+                    self._tm.process_scaled(self._src[slot], self._dst, nframes=n)
+                else:
+                    self._tm.process(self._src[slot], self._dst, nframes=n)   # synchronous for host frames
                 self._free.put(slot)
                 self.enc.stdin.write(dst_mv[:n * fout])
                 self.frames += n

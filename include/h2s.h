@@ -64,7 +64,9 @@ extern "C" {
  * (4:2:2 / 4:4:4 planar input on the CPU chain); h2s_set_input_tags (a
  * source's full-range and top-left chroma tags); h2s_preview_source_rgb24 /
  * _batch (the preview's source pane: the unconverted frame as RGB24);
- * h2s_set_dovi (Dolby Vision profile 5: per-frame RPU records).  No existing
+ * h2s_set_dovi (Dolby Vision profile 5: per-frame RPU records);
+ * h2s_scaled_size / h2s_process_scaled (convert and downscale in one call:
+ * scaled 4:2:0 output).  No existing
  * struct, signature or default behaviour changes, so the symbol's presence in
  * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -261,6 +263,10 @@ enum h2s_option {
 #define H2S_OPT_TEST_PEAK_CHUNK (H2S_OPT_PRIVATE_BASE + 3)
 /* peak statistics: blocks (partial records) per frame, 1..256 (default 64) */
 #define H2S_OPT_TEST_PEAK_BLOCKS (H2S_OPT_PRIVATE_BASE + 4)
+/* a query, not a setting: H2S_OK if the context has uploaded the scaled output's
+ * tap tables exactly `value` times, else H2S_E_INVALID_ARG (the count is in
+ * h2s_last_error) */
+#define H2S_OPT_TEST_SCALE_UPLOADS (H2S_OPT_PRIVATE_BASE + 5)
 #endif
 
 /* Kernel path h2s_process takes for a given frame pair (h2s_query_path). */
@@ -684,6 +690,55 @@ int h2s_preview_source_rgb24(h2s_ctx *ctx, const h2s_frames *in, uint8_t *rgb, i
 int h2s_preview_source_rgb24_batch(h2s_ctx *ctx, const h2s_frames *in, int nframes, uint8_t *rgb,
                                    int64_t rgb_linesize, int64_t rgb_frame_pitch, int out_w, int out_h,
                                    int matrix, int rgb_model, int rgb_location, void *hip_stream);
+
+/* ---- scaled 4:2:0 output: convert and downscale in one call ----------------
+ * The reference's chain definition has this tail: FFMPEG_FILTER
+ * (src/utils.py:46-49) is the export chain plus
+ * scale=W:H:force_original_aspect_ratio=decrease.  [EXT], parity unpinned like
+ * the rest of the preview tail.
+ * h2s_scaled_size: h2s_preview_size's aspect fit of an in_w x in_h frame in a
+ *   box_w x box_h box, each dimension then rounded down to even and not below
+ *   2: what a 4:2:0 deliverable needs.  This is ffmpeg's scale option
+ *   force_divisible_by=2, written from memory of libavfilter's scale_eval and
+ *   not checked against it.
+ * h2s_process_scaled: h2s_process, with out->width x out->height the target
+ *   size (`in` keeps the source size; out->bits == params.bits_out).  The
+ *   resize is a trailing scale= stage on the chain's quantised 4:2:0 output,
+ *   before the S8 expansion, on both pipelines, with peak_detect or Dolby
+ *   Vision records set (the chain in front is untouched):
+ *   - Depth: q is the chain's quantising depth (8 in H2S_MODE_COMPAT8,
+ *     bits_out in H2S_MODE_NATIVE and on the libplacebo branch at gamma 1);
+ *     the resize's source codes are the chain's q-bit codes, what h2s_process
+ *     would write >> (bits_out - q).
+ *   - Planes: luma W x H -> ow x oh, each chroma plane W/2 x H/2 -> ow/2 x
+ *     oh/2; ow and oh even and >= 2 (else H2S_E_INVALID_ARG).
+ *   - Taps: those of h2s_preview_rgb24's resize: swscale bicubic B = 0,
+ *     C = 0.6, centre-aligned, support widened by the ratio when downscaling,
+ *     normalised float32 weights, source indices clamped at the edges.  No
+ *     chroma-siting correction, as in the preview.
+ *   - Arithmetic: float32, the horizontal pass then the vertical one, each an
+ *     ascending fmaf chain from 0; v = floor(acc + 0.5) clamped to
+ *     [0, 2^q - 1]; then S8 (H2S_EXPAND_SHIFT / _REPLICATE) to bits_out.
+ *   - Limits: source / target <= 12 per axis and target <= 4 * 8192, else
+ *     H2S_E_UNSUPPORTED.
+ *   - Equal size: the call is h2s_process and nothing else (byte-identical).
+ *   It honours h2s_set_frame_layout on both sides (planar or semi-planar
+ *   output, padded pitches), h2s_set_input_subsampling, h2s_set_input_tags and
+ *   h2s_set_dovi exactly as h2s_process does, and its other errors are
+ *   h2s_process's.  Device -> device is asynchronous on hip_stream; a
+ *   host-resident set is staged, and the call then returns after the stream
+ *   has finished.  The full-size intermediate lives in a context-owned device
+ *   scratch (planar 4:2:0 at bits_out) of at most 16 frames: a longer batch
+ *   runs in chunks, stream-ordered, so the dynamic peak's state sees the
+ *   frames in order and the output does not depend on the chunking.  The tap
+ *   tables are cached in the context per (W, H, ow, oh) and uploaded once: a
+ *   steady-state call makes no host -> device copy and no synchronisation; a
+ *   new size waits for the context's queued launches first.  With
+ *   h2s_set_timing the resize launch is one more entry of the record, after
+ *   its chunk's h2s_process entry. */
+int h2s_scaled_size(int in_w, int in_h, int box_w, int box_h, int *out_w, int *out_h);
+int h2s_process_scaled(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out,
+                       int nframes, void *hip_stream);
 
 /* ---- .cube helpers (tools/generate_lut.py:28-119; lut3d's .cube parser) --
  * h2s_cube_generate: the BT.2020->BT.709 lattice, n^3 triples, .cube order,
