@@ -595,6 +595,8 @@ static int process_pipelined(h2s_ctx* c, KParams k, const h2s_frames* in, const 
 int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
                    Format in_fmt, Format out_fmt, int dovi_f0) {
   if (nframes < 0) return fail(c, H2S_E_INVALID_ARG, "nframes < 0");
+  // the 4:2:0 front-end (h2s_set_input_decimation): it calls back with the 4:2:0 set
+  if (decimating(c, in_fmt)) return process_decimated(c, in, out, nframes, s, in_fmt, out_fmt, dovi_f0);
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
@@ -828,33 +830,67 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
   if (stage < H2S_STAGE_LINEAR || stage > H2S_STAGE_YUV) return fail(c, H2S_E_INVALID_ARG, "bad stage");
   if (!out_rgb) return fail(c, H2S_E_INVALID_ARG, "out_rgb is NULL");
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (!decimating(c, c->in_fmt)) return debug_float(c, in, c->in_fmt, stage, out_rgb, out_location, s);
+  // the 4:2:0 front-end first (debug_float waits for s, so the scratch is free on return)
+  Decimated d;
+  h2s_frames view;
+  int rc;
+  if ((rc = decimate_begin(c, in, 1, s, c->in_fmt, &d))) return rc;
+  DeviceGuard g(c->device);
+  if ((rc = decimate_chunk(c, d, in, 1, s, &view))) return queued_exit(c, s, rc);
+  rc = debug_float(c, &view, d.fmt, stage, out_rgb, out_location, s);
+  const int rc_end = decimate_end(c, s);
+  return rc ? rc : rc_end;
+}
+
+int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
+  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
+  if (!decimating(c, c->in_fmt)) return query_path(c, in, out, c->in_fmt);
+  // the answer for the 4:2:0 set the front-end makes (its scratch is 256-byte aligned, like a staged set)
+  if (!c->params_set) return fail(c, H2S_E_INVALID_ARG, "h2s_set_params was not called");
+  if (int rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt)) return rc;
+  const uint8_t* fake = (const uint8_t*)(uintptr_t)4096;
+  Format f420 = c->in_fmt;
+  f420.sub = H2S_SUB_420, f420.loc = H2S_CHROMA_LEFT;
+  const h2s_frames view = decimated_view(in, c->in_fmt, fake, fake);
+  return query_path(c, &view, out, f420);
+}
+
+}  // extern "C"
+
+namespace h2s {
+namespace host {
+
+// h2s_debug_float for a set of the form given (the context's own, or the 4:2:0 set of its front-end)
+int debug_float(h2s_ctx* c, const h2s_frames* in, Format in_fmt, int stage, float* out_rgb, int out_location,
+                hipStream_t s) {
   KParams k;
   int rc = prepare(c, &k);
   if (rc) return rc;
-  if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
-  if ((rc = check_dovi(c, k, c->in_fmt, 0, 1))) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
+  if ((rc = check_subsampling(c, k, in_fmt))) return rc;
+  if ((rc = check_dovi(c, k, in_fmt, 0, 1))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_fmt))) return rc;
   DeviceGuard g(c->device);
-  hipStream_t s = (hipStream_t)hip_stream;
   const size_t npx = (size_t)in->width * in->height, ob = npx * 3 * sizeof(float);
   // scratch: a tight device copy of the input (host input), the float planes
   // (host output) and one output frame for the tile kernel's own stores
   h2s_frames fo{};
   fo.width = in->width, fo.height = in->height, fo.bits = c->params.bits_out, fo.location = H2S_LOC_DEVICE;
-  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in, c->in_fmt) + 255) / 256 * 256 : 0;
+  const size_t ib = in->location == H2S_LOC_HOST ? (frame_bytes(in, in_fmt) + 255) / 256 * 256 : 0;
   const size_t fb = (frame_bytes(&fo, PLANAR_420) + 255) / 256 * 256, pb = out_location == H2S_LOC_HOST ? ob : 0;
   Dev<uint8_t> scratch;  // freed on every exit, after s has been waited for
   if ((rc = scratch.reserve(c, ib + fb + pb + 256, "debug"))) return rc;
   uint8_t* base = scratch;
-  const h2s_frames din = device_view(in, base, c->in_fmt);
+  const h2s_frames din = device_view(in, base, in_fmt);
   hipError_t e;
-  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, c->in_fmt)) != hipSuccess)
+  if (in->location == H2S_LOC_HOST && (e = copy_frames(&din, in, 1, s, in_fmt)) != hipSuccess)
     return hip_fail(c, e, "debug copy");
   fo = tight(&fo, base + ib, PLANAR_420);   // (the call's own planar scratch frame)
   float* dout = out_location == H2S_LOC_HOST ? (float*)(base + ib + fb) : out_rgb;
-  fill_geometry(&k, &din, &fo, 1, c->in_fmt, PLANAR_420);
+  fill_geometry(&k, &din, &fo, 1, in_fmt, PLANAR_420);
   const bool out8 = c->params.bits_out == 8;
-  const Route r{choose_path(c, k, &din, &fo, out8, c->in_fmt, PLANAR_420), false, out8, c->in_fmt, PLANAR_420, s};
+  const Route r{choose_path(c, k, &din, &fo, out8, in_fmt, PLANAR_420), false, out8, in_fmt, PLANAR_420, s};
   // the generic debug kernel covers every pixel; on the tile path the tile
   // kernel's debug instance then rewrites the tile columns with its own values
   // (where it has one: there are no debug instances of the tile kernel for
@@ -876,6 +912,27 @@ int h2s_debug_float(h2s_ctx* c, const h2s_frames* in, int stage, float* out_rgb,
   if (e != hipSuccess) return hip_fail(c, e, "debug kernel");
   return 0;
 }
+
+// h2s_query_path for an input set of the form given
+int query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, Format in_fmt) {
+  KParams k;
+  int rc = prepare(c, &k);
+  if (rc) return rc;
+  if ((rc = check_subsampling(c, k, in_fmt))) return rc;
+  if ((rc = check_dovi(c, k, in_fmt, 0, 1))) return rc;
+  if ((rc = check_frames(c, in, c->params.bits_in, "input", in_fmt))) return rc;
+  if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_fmt))) return rc;
+  // host sets are staged into tight device copies, whose alignment decides
+  uint8_t* fake = (uint8_t*)(uintptr_t)4096;
+  const h2s_frames din = device_view(in, fake, in_fmt), dout = device_view(out, fake, c->out_fmt);
+  fill_geometry(&k, &din, &dout, 1, in_fmt, c->out_fmt);
+  return choose_path(c, k, &din, &dout, c->params.bits_out == 8, in_fmt, c->out_fmt);
+}
+
+}  // namespace host
+}  // namespace h2s
+
+extern "C" {
 
 int h2s_set_option(h2s_ctx* c, int key, int64_t value) {
   if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
@@ -943,22 +1000,6 @@ int h2s_set_input_tags(h2s_ctx* c, int range, int chroma_location) {
   // (only the arguments of later launches change: nothing queued reads these)
   c->in_fmt.range = range, c->in_fmt.loc = chroma_location;
   return 0;
-}
-
-int h2s_query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out) {
-  if (!c) return fail(nullptr, H2S_E_INVALID_ARG, "ctx is NULL");
-  KParams k;
-  int rc = prepare(c, &k);
-  if (rc) return rc;
-  if ((rc = check_subsampling(c, k, c->in_fmt))) return rc;
-  if ((rc = check_dovi(c, k, c->in_fmt, 0, 1))) return rc;
-  if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
-  if ((rc = check_frames(c, out, c->params.bits_out, "output", c->out_fmt))) return rc;
-  // host sets are staged into tight device copies, whose alignment decides
-  uint8_t* fake = (uint8_t*)(uintptr_t)4096;
-  const h2s_frames din = device_view(in, fake, c->in_fmt), dout = device_view(out, fake, c->out_fmt);
-  fill_geometry(&k, &din, &dout, 1, c->in_fmt, c->out_fmt);
-  return choose_path(c, k, &din, &dout, c->params.bits_out == 8, c->in_fmt, c->out_fmt);
 }
 
 int h2s_set_timing(h2s_ctx* c, int enabled) {

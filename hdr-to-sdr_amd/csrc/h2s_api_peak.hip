@@ -224,17 +224,40 @@ int h2s_peak_stats(h2s_ctx* c, const h2s_frames* in, int nframes, double* fmax, 
   KParams k;
   int rc = prepare(c, &k, false);  // the statistics need no LUT
   if (rc) return rc;
-  if (c->in_fmt.sub != H2S_SUB_420)
+  const bool dec = decimating(c, c->in_fmt);   // (h2s_set_input_decimation: the statistics of the 4:2:0 set)
+  if (c->in_fmt.sub != H2S_SUB_420 && !dec)
     return fail(c, H2S_E_UNSUPPORTED, "h2s_peak_stats reads 4:2:0 input only (h2s_set_input_subsampling is 4:2:2 / 4:4:4)");
-  if ((rc = check_dovi(c, k, c->in_fmt, 0, nframes))) return rc;
+  // (behind the front-end the records are judged for the 4:2:0 set it makes: left-sited, whatever the tag)
+  Format dv_fmt = c->in_fmt;
+  if (dec) dv_fmt.sub = H2S_SUB_420, dv_fmt.loc = H2S_CHROMA_LEFT;
+  if ((rc = check_dovi(c, k, dv_fmt, 0, nframes))) return rc;
   if ((rc = check_frames(c, in, c->params.bits_in, "input", c->in_fmt))) return rc;
   if (in->location != H2S_LOC_DEVICE) return fail(c, H2S_E_INVALID_ARG, "h2s_peak_stats takes device frames");
   if (nframes == 0) return 0;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)hip_stream;
-  h2s_frames out = *in;                       // geometry only: the statistics read the input planes
-  fill_geometry(&k, in, &out, nframes, c->in_fmt, PLANAR_420);
-  if ((rc = peak_order(c, s)) || (rc = frame_stats(c, k, s, nullptr, nullptr))) return rc;
+  if ((rc = peak_order(c, s))) return rc;
+  if (!dec) {
+    h2s_frames out = *in;                       // geometry only: the statistics read the input planes
+    fill_geometry(&k, in, &out, nframes, c->in_fmt, PLANAR_420);
+    if ((rc = frame_stats(c, k, s, nullptr, nullptr))) return rc;
+  } else {
+    // chunk by chunk behind the front-end; d_fstat takes the whole call's frames first (a grown buffer is a new one)
+    Decimated d;
+    if ((rc = decimate_begin(c, in, nframes, s, c->in_fmt, &d)) ||
+        (rc = c->d_fstat.reserve(c, (size_t)nframes * sizeof(double2), "peak statistics")))
+      return rc;
+    for (int f0 = 0; f0 < nframes; f0 += d.per) {
+      const int nf = std::min(d.per, nframes - f0);
+      const h2s_frames ci = frames_at(in, f0);
+      h2s_frames view;
+      if ((rc = decimate_chunk(c, d, &ci, nf, s, &view))) return queued_exit(c, s, rc);
+      fill_geometry(&k, &view, &view, nf, d.fmt, PLANAR_420);
+      k.dovi_f0 = f0;   // (a chunk's Dolby Vision records count frames of the call)
+      if ((rc = frame_stats(c, k, s, nullptr, nullptr, f0))) return queued_exit(c, s, rc);
+    }
+    if ((rc = decimate_end(c, s))) return queued_exit(c, s, rc);
+  }
   std::vector<double2> st(nframes);
   hipError_t e = hipMemcpyAsync(st.data(), c->d_fstat, nframes * sizeof(double2), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);

@@ -8,6 +8,7 @@
 //   h2s_api_preview.hip  the two preview panes
 //   h2s_api_dovi.hip     Dolby Vision profile 5: the records' validation and upload
 //   h2s_api_scale.hip    the scaled 4:2:0 output (h2s_process_scaled)
+//   h2s_api_decimate.hip the 4:2:0 front-end of a 4:2:2 / 4:4:4 set (h2s_set_input_decimation)
 //
 // Everything declared here has hidden visibility: the library's dynamic
 // symbols are the h2s_* calls of include/h2s.h and nothing else.
@@ -279,6 +280,11 @@ struct h2s_ctx {
   h2s::host::Dev<uint8_t> d_scale;
   h2s::host::ScaleTaps scale_taps;
   h2s::host::Ordered scale_use;             // after the last scaled call (d_scale and the tables in use)
+  // the 4:2:0 front-end (h2s_set_input_decimation): a host chunk's staged
+  // source frames, then the decimated chroma of one chunk
+  int decimate = H2S_DECIMATE_OFF;
+  h2s::host::Dev<uint8_t> d_dec;
+  h2s::host::Ordered dec_use;               // after the last call that used d_dec
 };
 
 namespace h2s {
@@ -374,6 +380,30 @@ int process_frames(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int 
                    Format in_fmt, Format out_fmt, int dovi_f0 = 0);
 int upload_table(h2s_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* what);
 int note_launch(h2s_ctx* c, hipStream_t s);
+
+int debug_float(h2s_ctx* c, const h2s_frames* in, Format in_fmt, int stage, float* out_rgb, int out_location,
+                hipStream_t s);
+int query_path(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, Format in_fmt);
+
+// ---- h2s_api_decimate.hip ----
+
+// A call's use of the front-end: begin (the checks, the scratch, its ordering
+// on s), then chunk by chunk (at most d.per frames: stage a host chunk, launch
+// k_decimate420, and *view is the 4:2:0 set of Format d.fmt that the chain
+// reads: the chunk's luma in place, the chroma in the scratch), then end
+struct Decimated {
+  Format src_fmt, fmt;
+  int per = 0;               // frames of a chunk at the most
+  uint8_t *stage = nullptr, *chroma = nullptr;   // in c->d_dec
+};
+bool decimating(const h2s_ctx* c, Format in_fmt);
+h2s_frames decimated_view(const h2s_frames* in, Format in_fmt, const uint8_t* stage, const uint8_t* chroma);
+int decimate_begin(h2s_ctx* c, const h2s_frames* in, int nframes, hipStream_t s, Format in_fmt, Decimated* d);
+int decimate_chunk(h2s_ctx* c, const Decimated& d, const h2s_frames* in, int nf, hipStream_t s, h2s_frames* view,
+                   int run = 0);
+int decimate_end(h2s_ctx* c, hipStream_t s);
+int process_decimated(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
+                      Format in_fmt, Format out_fmt, int dovi_f0);
 
 // ---- h2s_api_dovi.hip ----
 

@@ -33,6 +33,8 @@ SUB_420, SUB_422, SUB_444 = 0, 1, 2   # enum h2s_subsampling (h2s_set_input_subs
 SUBSAMPLINGS = {'420': SUB_420, '422': SUB_422, '444': SUB_444}
 RANGE_LIMITED, RANGE_FULL = 0, 1       # enum h2s_range (h2s_set_input_tags)
 CHROMA_LEFT, CHROMA_TOPLEFT = 0, 1     # enum h2s_chroma_loc
+DECIMATE_OFF, DECIMATE_BICUBIC = 0, 1   # enum h2s_decimation (h2s_set_input_decimation)
+DECIMATIONS = {'off': DECIMATE_OFF, 'bicubic': DECIMATE_BICUBIC}
 COLOR_RANGES = {'tv': RANGE_LIMITED, 'pc': RANGE_FULL}   # ffprobe's color_range / chroma_location values
 CHROMA_LOCATIONS = {'left': CHROMA_LEFT, 'topleft': CHROMA_TOPLEFT}
 SRC_MATRIX_BT2020NC, SRC_MATRIX_BT709, SRC_MATRIX_BT601 = 0, 1, 2   # enum h2s_src_matrix (h2s_preview_source_rgb24)
@@ -71,7 +73,7 @@ EXPORTS = (
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
     'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch', 'h2s_set_dovi',
-    'h2s_scaled_size', 'h2s_process_scaled',
+    'h2s_scaled_size', 'h2s_process_scaled', 'h2s_set_input_decimation',
 )
 
 
@@ -198,6 +200,7 @@ def lib() -> ctypes.CDLL:
         'h2s_set_frame_layout': (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_int]),
         'h2s_set_input_subsampling': (ctypes.c_int, [c_ctx, ctypes.c_int]),
         'h2s_set_input_tags': (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_int]),
+        'h2s_set_input_decimation': (ctypes.c_int, [c_ctx, ctypes.c_int]),
         'h2s_preview_size': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         'h2s_preview_rgb24': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.c_void_p, ctypes.c_int64,

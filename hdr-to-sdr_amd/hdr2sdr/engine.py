@@ -36,6 +36,7 @@ class Tonemapper:
         self._layouts = ('planar', 'planar')   # what the context last got (h2s_set_frame_layout)
         self._subsampling = '420'              # ... (h2s_set_input_subsampling)
         self._tags = ('tv', 'left')            # ... (h2s_set_input_tags)
+        self._decimation = 'off'               # ... (h2s_set_input_decimation)
         self.dovi_records = 0                  # Dolby Vision records set (set_dovi; 0: off)
         if params is not None:
             self.set_params(params)
@@ -134,6 +135,21 @@ class Tonemapper:
             self._check(self._L.h2s_set_input_tags(self._ctx, _abi.COLOR_RANGES[color_range],
                                                    _abi.CHROMA_LOCATIONS[chroma_location]))
             self._tags = (color_range, chroma_location)
+
+    def set_input_decimation(self, mode: str = 'off') -> None:
+        """The 4:2:0 front-end of a 4:2:2 / 4:4:4 source batch ('off' |
+        'bicubic'; h2s_set_input_decimation).  'bicubic': every later call that
+        converts such a batch sees the 4:2:0 frames a swscale-bicubic chroma
+        decimation on the device makes of it, on either pipeline, with
+        peak_detect, and for semi-planar batches
+        (``FrameBatch(..., allow_semi_sub=True)``) too.  Unlike the layout,
+        subsampling and tags it is a setting of the context, not of a batch:
+        it stays until it is set again."""
+        if mode not in _abi.DECIMATIONS:
+            raise ValueError(f"input decimation must be 'off' or 'bicubic', got {mode!r}")
+        if mode != self._decimation:
+            self._check(self._L.h2s_set_input_decimation(self._ctx, _abi.DECIMATIONS[mode]))
+            self._decimation = mode
 
     def set_dovi(self, rpus: Any = None) -> None:
         """Dolby Vision profile 5 (h2s_set_dovi): None (or an empty sequence)

@@ -26,6 +26,13 @@ planes of H x W/2 or H x W samples: W * H * 2 or W * H * 3 samples per frame.
 The kernels read them at their own chroma resolution
 (h2s_set_input_subsampling); the output side is always 4:2:0.
 
+Semi-planar 4:2:2 / 4:4:4 source batches (p210le / p212le / p410le / p412le:
+what a hardware decoder hands out for such streams) exist only behind the
+explicit ``allow_semi_sub=True``: the Y plane, then one plane of (Cb, Cr) pairs
+with H rows of W/2 (4:2:2) or W (4:4:4) pairs, the code in the high bits of
+each word.  Only the 4:2:0 front-end reads them
+(Tonemapper.set_input_decimation('bicubic'), h2s_set_input_decimation).
+
 A source batch also carries two tags of its stream (``color_range`` 'tv' |
 'pc', ``chroma_location`` 'left' | 'topleft': ffprobe's fields of those names),
 which the kernels honour when they read it (h2s_set_input_tags): full-range
@@ -81,6 +88,8 @@ class FrameBatch:
     subsampling: str = '420'
     color_range: str = 'tv'
     chroma_location: str = 'left'
+    # admits layout='semi' with subsampling '422' / '444' (p210le / p212le / p410le / p412le)
+    allow_semi_sub: bool = False
 
     def __post_init__(self):
         if self.color_range not in COLOR_RANGES:
@@ -92,13 +101,14 @@ class FrameBatch:
             raise ValueError(f"layout must be 'planar' or 'semi', got {self.layout!r}")
         if self.subsampling not in SUBSAMPLINGS:
             raise ValueError(f"subsampling must be '420', '422' or '444', got {self.subsampling!r}")
-        if self.subsampling != '420' and self.layout == 'semi':
-            raise ValueError('4:2:2 / 4:4:4 batches are planar only (no p210 / p410)')
+        if self.subsampling != '420' and self.layout == 'semi' and not self.allow_semi_sub:
+            raise ValueError('4:2:2 / 4:4:4 batches are planar only (no p210 / p410) unless allow_semi_sub=True '
+                             '(read through the 4:2:0 front-end alone)')
 
     def _like(self, buf: Any, layout: 'str | None' = None) -> 'FrameBatch':
         """A batch over ``buf`` with this batch's geometry, form and tags."""
         return FrameBatch(buf, self.width, self.height, self.bits, self.layout if layout is None else layout,
-                          self.subsampling, self.color_range, self.chroma_location)
+                          self.subsampling, self.color_range, self.chroma_location, self.allow_semi_sub)
 
     # ---- constructors ---------------------------------------------------
     @staticmethod
@@ -115,24 +125,28 @@ class FrameBatch:
     @classmethod
     def empty_torch(cls, nframes: int, width: int, height: int, bits: int, device: Any,
                     layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
-                    chroma_location: str = 'left') -> 'FrameBatch':
+                    chroma_location: str = 'left', allow_semi_sub: bool = False) -> 'FrameBatch':
+        """``allow_semi_sub=True`` admits ``layout='semi'`` with ``subsampling``
+        '422' / '444' (p210le / p212le / p410le / p412le: the Y plane, then H
+        rows of W/2 or W (Cb, Cr) pairs, codes in the high bits); so do
+        empty_numpy and empty_pinned."""
         import torch
         dt = torch.uint8 if bits == 8 else torch.int16
         return cls(torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, device=device),
-                   width, height, bits, layout, subsampling, color_range, chroma_location)
+                   width, height, bits, layout, subsampling, color_range, chroma_location, allow_semi_sub)
 
     @classmethod
     def empty_numpy(cls, nframes: int, width: int, height: int, bits: int,
                     layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
-                    chroma_location: str = 'left') -> 'FrameBatch':
+                    chroma_location: str = 'left', allow_semi_sub: bool = False) -> 'FrameBatch':
         dt = np.uint8 if bits == 8 else np.uint16
         return cls(np.zeros(cls._shape(nframes, width, height, bits, subsampling), dtype=dt), width, height, bits,
-                   layout, subsampling, color_range, chroma_location)
+                   layout, subsampling, color_range, chroma_location, allow_semi_sub)
 
     @classmethod
     def empty_pinned(cls, nframes: int, width: int, height: int, bits: int,
                      layout: str = 'planar', subsampling: str = '420', color_range: str = 'tv',
-                     chroma_location: str = 'left') -> 'FrameBatch':
+                     chroma_location: str = 'left', allow_semi_sub: bool = False) -> 'FrameBatch':
         """Host batch in page-locked memory (DMA-able without a bounce copy:
         the host-buffer path of h2s_process then runs at PCIe speed). Falls
         back to pageable numpy memory when no GPU runtime is present."""
@@ -142,12 +156,13 @@ class FrameBatch:
                 dt = torch.uint8 if bits == 8 else torch.int16
                 t = torch.empty(cls._shape(nframes, width, height, bits, subsampling), dtype=dt, pin_memory=True)
                 a = t.numpy() if bits == 8 else t.numpy().view(np.uint16)
-                fb = cls(a, width, height, bits, layout, subsampling, color_range, chroma_location)
+                fb = cls(a, width, height, bits, layout, subsampling, color_range, chroma_location, allow_semi_sub)
                 fb._pin = t          # keep the pinned allocation alive
                 return fb
         except (ImportError, RuntimeError):
             pass
-        return cls.empty_numpy(nframes, width, height, bits, layout, subsampling, color_range, chroma_location)
+        return cls.empty_numpy(nframes, width, height, bits, layout, subsampling, color_range, chroma_location,
+                               allow_semi_sub)
 
     @classmethod
     def from_planes(cls, y: np.ndarray, u: np.ndarray, v: np.ndarray, bits: int,
@@ -185,11 +200,13 @@ class FrameBatch:
     @property
     def uv(self):
         """The interleaved plane of a semi-planar batch as [F, H/2, W/2, 2]
-        ((Cb, Cr) last); ``u`` / ``v`` of such a batch are strided views of it."""
+        ((Cb, Cr) last; a 4:2:2 / 4:4:4 batch: [F, H, W/2, 2] / [F, H, W, 2]);
+        ``u`` / ``v`` of such a batch are strided views of it."""
         if self.layout != 'semi':
             raise ValueError('uv is the interleaved plane of a semi-planar batch')
         w, h = self.width, self.height
-        return self.buf[:, w * h:].reshape(self.nframes, h // 2, w // 2, 2)
+        cxs, cys = _CHROMA_SHIFTS[self.subsampling]
+        return self.buf[:, w * h:].reshape(self.nframes, h >> cys, w >> cxs, 2)
 
     @property
     def y(self):
@@ -288,8 +305,8 @@ class FrameBatch:
         d.data[1] = base + ysz
         d.linesize[0] = w * sb
         if self.layout == 'semi':
-            # plane 1: the interleaved plane, a row of W samples; plane 2 unused (zero)
-            d.linesize[1] = w * sb
+            # plane 1: the interleaved plane, a row of W samples (4:4:4: 2 W); plane 2 unused (zero)
+            d.linesize[1] = 2 * (w >> cxs) * sb
             d.frame_pitch[0] = d.frame_pitch[1] = fpitch
         else:
             d.data[2] = base + ysz + csz

@@ -100,6 +100,10 @@ class PipePlan:
     # the deliverable's size (``scale=``); None: the source's
     out_width: 'int | None' = None
     out_height: 'int | None' = None
+    # where a libplacebo plan's 4:2:2 / 4:4:4 source becomes 4:2:0: 'cpu' (the
+    # decode side's swscale; the pipe is 4:2:0) or 'gpu' (the pipe carries the
+    # source's own subsampling and the context decimates: set_input_decimation)
+    decimate: str = 'cpu'
 
     def __post_init__(self):
         if self.out_width is None:
@@ -132,7 +136,7 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
                    mode: str = 'compat8', in_layout: str = 'planar', out_layout: str = 'planar',
                    in_subsampling: str = '420', in_range: str = 'tv',
                    in_chroma_location: str = 'left', dovi: Any = None,
-                   scale: 'Tuple[int, int] | None' = None) -> PipePlan:
+                   scale: 'Tuple[int, int] | None' = None, decimate: str = 'cpu') -> PipePlan:
     """Split a reference ``build()`` argv into decode/encode argvs + params.
 
     in_layout / out_layout ('planar' | 'semi' | 'auto'): the frame layout on
@@ -189,6 +193,19 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
     (``-s``, ``frame_bytes_out``) and the run loop converts and resizes each
     batch in one call (``Tonemapper.process_scaled``), with no second pass on
     the CPU.  With None every argv and every byte is as without the argument.
+
+    decimate ('cpu' | 'gpu'): where a libplacebo plan's 4:2:2 / 4:4:4 source
+    (``in_subsampling`` given, or 'auto' from ffprobe's ``pix_fmt``) becomes the
+    4:2:0 that the branch tone-maps.  'cpu' (the default: every argv and byte as
+    without the argument): the decode side's swscale, per frame, as above.
+    'gpu': the decode pipe keeps the source's own ``-pix_fmt`` (yuv422p1Xle /
+    yuv444p1Xle), the plan carries ``decimate='gpu'`` and the run loop sets the
+    context's 4:2:0 front-end (``Tonemapper.set_input_decimation('bicubic')``;
+    'off' for every other plan), so the chroma decimation runs on the device in
+    front of the conversion.  A
+    CPU-chain plan ignores it (it reads the source natively); a 4:2:0 source
+    needs none.  A semi-planar 4:2:2 / 4:4:4 decode pipe stays refused: the
+    software decode pipe is planar.
 
     Raises ValueError for an argv without a tone-map filter graph, and for a
     Dolby Vision profile 5 source without ``dovi`` (its RPU cannot cross the
@@ -267,7 +284,11 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
         raise ValueError(f"in_subsampling must be '420', '422', '444' or 'auto', got {in_subsampling!r}")
     if in_subsampling == 'auto':
         in_subsampling = SOURCE_SUBSAMPLING.get(str(properties.get('pix_fmt') or ''), '420')
-    if params.resolved_pipeline() == 'libplacebo':
+    if decimate not in ('cpu', 'gpu'):
+        raise ValueError(f"decimate must be 'cpu' or 'gpu', got {decimate!r}")
+    if params.resolved_pipeline() != 'libplacebo' or in_subsampling == '420':
+        decimate = 'cpu'           # nothing to decimate in front of the chain
+    if params.resolved_pipeline() == 'libplacebo' and decimate == 'cpu':
         in_subsampling = '420'     # format=p010,hwupload: the reference's own 4:2:0
     if in_subsampling != '420' and in_layout == 'semi':
         raise ValueError('4:2:2 / 4:4:4 decode pipes are planar only (no p210 / p410)')
@@ -300,7 +321,7 @@ def plan_from_argv(argv: 'list[str]', properties: 'dict[str, Any]', hdr: 'dict[s
                     input_path=input_path, output_path=output_path, reference_argv=argv,
                     in_layout=in_layout, layout=out_layout, in_subsampling=in_subsampling,
                     in_range=in_range, in_chroma_location=in_chroma_location, dovi=dovi,
-                    out_width=OW, out_height=OH)
+                    out_width=OW, out_height=OH, decimate=decimate)
 
 
 def _read_full(stream: Any, buf: memoryview) -> int:
@@ -334,6 +355,13 @@ class H2SProcess:
         self.enc = popen(plan.encode, stdin=subprocess.PIPE, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL)
         self.stderr = io.TextIOWrapper(self.enc.stderr, encoding='utf-8', errors='replace')
         p = plan.params
+        # the 4:2:0 front-end of the libplacebo branch, on the device; off for every other plan, so a context
+        # that served such a plan reads a later plan's 4:2:2 / 4:4:4 source natively again
+        # (a tonemapper object without the setting has nothing to switch off)
+        if plan.decimate == 'gpu':
+            tonemapper.set_input_decimation('bicubic')
+        elif hasattr(tonemapper, 'set_input_decimation'):
+            tonemapper.set_input_decimation('off')
         # page-locked staging: the pipe bytes go straight to / from HBM by DMA.
         # `depth` input slots let the decoder run ahead while the GPU stage
         # and the encoder work on earlier batches.

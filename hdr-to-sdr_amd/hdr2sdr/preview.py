@@ -197,11 +197,15 @@ class Previewer:
     FFMPEG_FILTER_LEGACY_NO_LUT's closed-form gamut path on the CPU chain
     (src/utils.py:57-60) and libplacebo's own BT.709 conversion on the GPU
     one.  Each preview frame starts from a fresh peak state, as each of the
-    reference's preview ffmpeg runs does."""
+    reference's preview ffmpeg runs does.  ``decimate`` ('off' | 'bicubic'):
+    the converted pane's 4:2:0 front-end for a 4:2:2 / 4:4:4 source
+    (``Tonemapper.set_input_decimation``: what a libplacebo preview of such a
+    source needs); the source pane shows the frames as decoded either way."""
 
     def __init__(self, device: int = 0, tonemapper: str = 'reinhard', lut_enabled: bool = True,
                  bits_in: int = 10, transfer: str = 'smpte2084', lattice: Optional[np.ndarray] = None,
-                 use_gpu: bool = False, params: Optional[TonemapParams] = None, dovi: Any = None, **kw: Any):
+                 use_gpu: bool = False, params: Optional[TonemapParams] = None, dovi: Any = None,
+                 decimate: str = 'off', **kw: Any):
         from .engine import Tonemapper
         if dovi is not None and params is None:
             use_gpu = True     # a Dolby Vision profile 5 source previews through libplacebo, GPU toggle or not
@@ -212,6 +216,7 @@ class Previewer:
         self.params = params
         lut_enabled = params.lut_enabled
         self._tm = Tonemapper(device, self.params)
+        self._tm.set_input_decimation(decimate)
         if lut_enabled:
             self._tm.set_lut(lattice if lattice is not None else _lut.generate_lattice(_lut.LUT_SIZE))
         if dovi is not None:

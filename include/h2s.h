@@ -66,7 +66,8 @@ extern "C" {
  * _batch (the preview's source pane: the unconverted frame as RGB24);
  * h2s_set_dovi (Dolby Vision profile 5: per-frame RPU records);
  * h2s_scaled_size / h2s_process_scaled (convert and downscale in one call:
- * scaled 4:2:0 output).  No existing
+ * scaled 4:2:0 output); h2s_set_input_decimation (a 4:2:2 / 4:4:4 source
+ * decimated to 4:2:0 on the device in front of either pipeline).  No existing
  * struct, signature or default behaviour changes, so the symbol's presence in
  * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -140,6 +141,9 @@ enum h2s_subsampling { H2S_SUB_420 = 0, H2S_SUB_422 = 1, H2S_SUB_444 = 2 };
  * The output side is always limited range. */
 enum h2s_range { H2S_RANGE_LIMITED = 0, H2S_RANGE_FULL = 1 };
 enum h2s_chroma_loc { H2S_CHROMA_LEFT = 0, H2S_CHROMA_TOPLEFT = 1 };
+
+/* The 4:2:0 front-end of a 4:2:2 / 4:4:4 input set (h2s_set_input_decimation). */
+enum h2s_decimation { H2S_DECIMATE_OFF = 0, H2S_DECIMATE_BICUBIC = 1 };
 
 /* Debug stages for h2s_debug_float: three float planes per pixel.
  * 1..4: R, G, B after the stage.  5: the quantiser's inputs, before rounding:
@@ -468,7 +472,8 @@ int h2s_set_frame_layout(h2s_ctx *ctx, int in_layout, int out_layout);
  *   - H2S_LAYOUT_SEMI on the input side (p210 / p410);
  *   - the libplacebo pipeline (params resolve to H2S_PIPE_LIBPLACEBO, hence
  *     peak_detect too): the reference uploads format=p010 there, i.e. 4:2:0;
- *   - h2s_peak_stats. */
+ *   - h2s_peak_stats.
+ * h2s_set_input_decimation lifts all three by decimating to 4:2:0 first. */
 int h2s_set_input_subsampling(h2s_ctx *ctx, int subsampling);
 
 /* ---- input source tags (enum h2s_range, enum h2s_chroma_loc; default
@@ -495,6 +500,45 @@ int h2s_set_input_subsampling(h2s_ctx *ctx, int subsampling);
  * Only the arguments of later launches change, so the call does not wait for
  * queued work.  An unknown value or a NULL ctx is H2S_E_INVALID_ARG. */
 int h2s_set_input_tags(h2s_ctx *ctx, int range, int chroma_location);
+
+/* ---- input decimation (enum h2s_decimation; default OFF) -------------------
+ * The stage the reference's GPU chain starts with (format=p010,hwupload:
+ * whatever the decoder produced, ffmpeg's auto-inserted swscale makes 4:2:0 of
+ * it first, src/utils.py:431), as a device front-end.  OFF: every call behaves
+ * and refuses exactly as h2s_set_input_subsampling says.  BICUBIC, while the
+ * context's input subsampling is 4:2:2 or 4:4:4: every call that converts
+ * `in` sees the 4:2:0 frames the front-end makes of it, on either pipeline:
+ * h2s_process, h2s_process_scaled, h2s_query_path (it answers for the 4:2:0
+ * set), h2s_debug_float, h2s_peak_stats and h2s_preview_rgb24 / _batch; with
+ * peak_detect, with Dolby Vision records, with planar or semi-planar input
+ * (p210le / p212le / p410le / p412le: words code << (16 - b)), device or host
+ * frames.  With 4:2:0 input the setting has no effect, and
+ * h2s_preview_source_rgb24 / _batch (the source as decoded) ignore it.
+ * Model ([EXT], parity unpinned like the rest of the pixel stages; DESIGN.md
+ * 4.14): S6's swscale-bicubic chroma model (H2S_CHROMA_BICUBIC; B = 0,
+ * C = 0.6), for input depth b:
+ *   - Luma is untouched: read in place from the caller's surface.
+ *   - 4:4:4: horizontally 7 taps on source columns 2k-3 .. 2k+3 (left-sited).
+ *   - 4:4:4 and 4:2:2: vertically 8 taps on source chroma rows 2m-3 .. 2m+4
+ *     (centred: the `left` 4:2:0 siting).  4:2:2: that pass alone.
+ *   - Indices are clamped to the plane (replicate).
+ *   - Float32 on the integer codes, the vertical pass then the horizontal one,
+ *     each an ascending fmaf chain from 0; v = floor(acc + 0.5) clamped to
+ *     [0, 2^b - 1].  Range-agnostic: full-range codes pass through.
+ *   - The chain behind it runs with the context's range tag and chroma
+ *     location LEFT (a top-left tag on a 4:2:2 / 4:4:4 set has no effect, as
+ *     without the front-end), on a 4:2:0 set of the context's own input layout
+ *     and depth whose luma is the caller's and whose chroma is a context-owned
+ *     device scratch of at most 16 frames: a longer batch runs in chunks,
+ *     stream-ordered on hip_stream, so the dynamic peak's state sees the frames
+ *     in order and the output does not depend on the chunking.  A host-resident
+ *     `in` is staged chunk by chunk on hip_stream (serially: not the
+ *     three-stream pipeline of h2s_process).
+ * With h2s_set_timing the front-end launch is one more entry of the record, in
+ * front of its chunk's conversion entry.  Only the arguments of later launches
+ * change, so the call does not wait for queued work.  An unknown value or a
+ * NULL ctx is H2S_E_INVALID_ARG. */
+int h2s_set_input_decimation(h2s_ctx *ctx, int mode);
 
 /* ---- Dolby Vision profile 5 (default: off) ---------------------------------
  * A profile-5 stream has no HDR10-compatible base layer: its codes are
