@@ -13,9 +13,13 @@ using h2s::ScalePlane;
 
 namespace {
 
-constexpr int kChunk = 16;   // frames of scratch at the most
-
 long long round_up(long long v, long long a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+// (library-private, h2s_host.h: h2s_process_rgb runs the same scratch, tables and resize launch)
+namespace h2s {
+namespace host {
 
 // the chain's output of one chunk: planar 4:2:0 at `bits`, every row start
 // 16-byte aligned (k_scale420 reads it in 16-byte pieces; the tile kernel
@@ -62,6 +66,11 @@ int ensure_taps(h2s_ctx* c, int W, int H, int ow, int oh, hipStream_t s) {
   return 0;
 }
 
+}  // namespace host
+}  // namespace h2s
+
+namespace {
+
 // One entry of the launch.  The rows a block owns: the most (up to
 // SCALE_MAX_ROWS) whose source rows, with the entry's other pieces, fit the LDS
 // budget: the smaller one while that leaves SCALE_ROWS_SMALL rows, else the
@@ -107,6 +116,11 @@ bool rows_aligned16(const h2s_frames* f, Format fmt) {
   return true;
 }
 
+}  // namespace
+
+namespace h2s {
+namespace host {
+
 // the launch of one chunk: mid (the chain's frames) -> dout
 int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int nf, Format out_fmt, hipStream_t s) {
   KParams g{};   // the two sets as the conversion kernels bind them (semi-planar: plane 2 aliases plane 1)
@@ -138,7 +152,8 @@ int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int 
   return e == hipSuccess ? 0 : hip_fail(c, e, "scale kernel launch");
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace h2s
 
 extern "C" {
 

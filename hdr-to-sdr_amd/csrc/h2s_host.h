@@ -9,6 +9,7 @@
 //   h2s_api_dovi.hip     Dolby Vision profile 5: the records' validation and upload
 //   h2s_api_scale.hip    the scaled 4:2:0 output (h2s_process_scaled)
 //   h2s_api_decimate.hip the 4:2:0 front-end of a 4:2:2 / 4:4:4 set (h2s_set_input_decimation)
+//   h2s_api_rgb.hip      the RGB tensor output (h2s_process_rgb)
 //
 // Everything declared here has hidden visibility: the library's dynamic
 // symbols are the h2s_* calls of include/h2s.h and nothing else.
@@ -404,6 +405,13 @@ int decimate_chunk(h2s_ctx* c, const Decimated& d, const h2s_frames* in, int nf,
 int decimate_end(h2s_ctx* c, hipStream_t s);
 int process_decimated(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
                       Format in_fmt, Format out_fmt, int dovi_f0);
+
+// ---- h2s_api_scale.hip (shared with h2s_api_rgb.hip) ----
+
+constexpr int kChunk = 16;   // frames of the scaled output's scratch at the most
+h2s_frames scratch_frames(int W, int H, int bits, uint8_t* base);
+int ensure_taps(h2s_ctx* c, int W, int H, int ow, int oh, hipStream_t s);
+int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int nf, Format out_fmt, hipStream_t s);
 
 // ---- h2s_api_dovi.hip ----
 

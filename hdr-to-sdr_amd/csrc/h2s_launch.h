@@ -1,6 +1,6 @@
 // h2s_launch.h — the one declaration of every host-callable kernel launcher.
 // Included by the unit that defines a launcher (h2s_kernels.hip, h2s_peak.hip,
-// h2s_fast.hip, h2s_preview.hip, h2s_scale.hip, h2s_decimate.hip) and by every unit that calls one (the host
+// h2s_fast.hip, h2s_preview.hip, h2s_scale.hip, h2s_decimate.hip, h2s_rgb.hip) and by every unit that calls one (the host
 // units, h2s_testhooks.hip), so a signature or an
 // enum value that drifts apart is a compile error, not a misrouted launch.
 #pragma once
@@ -19,6 +19,7 @@ struct PeakTail;
 struct SrcPreviewParams;  // h2s_srcprev.h
 struct ScaleParams;       // h2s_scale.h
 struct DecimateParams;    // h2s_decimate.h
+struct RgbParams;         // h2s_rgb.h
 
 // launch_process's form: PF_VEC the rows allow vector accesses, PF_OUT8 8-bit
 // output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma into P.chr444)
@@ -61,5 +62,9 @@ hipError_t launch_scale420(const ScaleParams& P, int src_bps, int nframes, hipSt
 // h2s_decimate.hip: the chroma of nframes 4:2:2 / 4:4:4 frames (sub: enum h2s_subsampling) to 4:2:0 in one
 // launch; it fills P's run and piece counts (run > 0: that run length, a test's; else its own pick)
 hipError_t launch_decimate420(const DecimateParams& P, int sub, bool semi, int nframes, int run, hipStream_t s);
+
+// h2s_rgb.hip: nframes planar 4:2:0 scratch frames to R'G'B' in one launch (src_bps: bytes of a scratch sample;
+// dtype, layout: enum h2s_rgb_dtype, enum h2s_rgb_layout); it fills P's run and row-pair counts
+hipError_t launch_rgb420(const RgbParams& P, int src_bps, int dtype, int layout, int nframes, hipStream_t s);
 
 }  // namespace h2s

@@ -73,8 +73,13 @@ EXPORTS = (
     'h2s_peak_state', 'h2s_peak_stats', 'h2s_peak_feed', 'h2s_set_option', 'h2s_query_path',
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
     'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch', 'h2s_set_dovi',
-    'h2s_scaled_size', 'h2s_process_scaled', 'h2s_set_input_decimation',
+    'h2s_scaled_size', 'h2s_process_scaled', 'h2s_set_input_decimation', 'h2s_process_rgb',
 )
+RGB_U8, RGB_F16, RGB_BF16, RGB_F32 = 0, 1, 2, 3   # enum h2s_rgb_dtype (h2s_process_rgb)
+RGB_DTYPES = {'uint8': RGB_U8, 'float16': RGB_F16, 'bfloat16': RGB_BF16, 'float32': RGB_F32}
+RGB_ELEM_BYTES = {RGB_U8: 1, RGB_F16: 2, RGB_BF16: 2, RGB_F32: 4}
+RGB_HWC, RGB_CHW = 0, 1                           # enum h2s_rgb_layout
+RGB_LAYOUTS = {'hwc': RGB_HWC, 'chw': RGB_CHW}
 
 
 class H2SParams(ctypes.Structure):
@@ -122,6 +127,22 @@ class H2SFrames(ctypes.Structure):
         ('height', ctypes.c_int32),
         ('bits', ctypes.c_int32),
         ('location', ctypes.c_int32),
+    ]
+
+
+class H2SRgbFrames(ctypes.Structure):
+    """h2s_rgb_frames: the device tensor h2s_process_rgb writes."""
+    _fields_ = [
+        ('data', ctypes.c_void_p),
+        ('width', ctypes.c_int32),
+        ('height', ctypes.c_int32),
+        ('dtype', ctypes.c_int32),
+        ('layout', ctypes.c_int32),
+        ('row_pitch', ctypes.c_int64),
+        ('plane_pitch', ctypes.c_int64),
+        ('frame_pitch', ctypes.c_int64),
+        ('scale', ctypes.c_float * 3),
+        ('bias', ctypes.c_float * 3),
     ]
 
 
@@ -222,6 +243,8 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         'h2s_process_scaled': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SFrames),
                                               ctypes.c_int, ctypes.c_void_p]),
+        'h2s_process_rgb': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SRgbFrames),
+                                           ctypes.c_int, ctypes.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

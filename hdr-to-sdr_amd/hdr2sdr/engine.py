@@ -18,6 +18,84 @@ from .frames import FrameBatch
 from . import lut as _lut
 
 
+# ---- the RGB tensor output's argument checks (Tonemapper.process_rgb) --------
+def rgb_dtype(dtype: Any) -> 'tuple[int, Any]':
+    """(enum h2s_rgb_dtype, torch dtype) of 'uint8' | 'float16' | 'bfloat16' |
+    'float32' or the torch dtype of that name."""
+    import torch
+    name = dtype if isinstance(dtype, str) else str(dtype).replace('torch.', '')
+    if name not in _abi.RGB_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(_abi.RGB_DTYPES)} (or the torch dtype), got {dtype!r}")
+    return _abi.RGB_DTYPES[name], getattr(torch, name)
+
+
+def rgb_normalisation(code: int, mean: Any, std: Any) -> 'tuple[list[float], list[float]]':
+    """(scale, bias) with out = scale * v + bias for (v - mean) / std."""
+    if mean is None and std is None:
+        return [1.0] * 3, [0.0] * 3
+    if code == _abi.RGB_U8:
+        raise ValueError('mean / std normalisation is for the float dtypes (uint8 holds the 0..255 picture)')
+    m = [0.0] * 3 if mean is None else [float(v) for v in mean]
+    s = [1.0] * 3 if std is None else [float(v) for v in std]
+    if len(m) != 3 or len(s) != 3:
+        raise ValueError('mean and std are three floats each (R, G, B)')
+    if not all(np.isfinite(m + s)) or any(v == 0.0 for v in s):
+        raise ValueError('mean and std must be finite, and std non-zero')
+    return [1.0 / v for v in s], [-a / v for a, v in zip(m, s)]
+
+
+def check_rgb_size(w: int, h: int) -> None:
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise ValueError(f'the RGB target needs even width and height >= 2, got {w}x{h}')
+
+
+def rgb_tensor_size(out: Any, layout: str) -> 'tuple[int, int]':
+    """(width, height) of an N x 3 x H x W ('chw') or N x H x W x 3 ('hwc') tensor."""
+    if out.dim() != 4 or out.shape[1 if layout == 'chw' else 3] != 3:
+        want = 'N x 3 x H x W' if layout == 'chw' else 'N x H x W x 3'
+        raise ValueError(f'out must be {want} for layout {layout!r}, got {tuple(out.shape)}')
+    return (int(out.shape[3]), int(out.shape[2])) if layout == 'chw' else (int(out.shape[2]), int(out.shape[1]))
+
+
+def rgb_frames(out: Any, code: int, layout: str, scale: Any, bias: Any, nframes: int) -> _abi.H2SRgbFrames:
+    """The h2s_rgb_frames record of a torch tensor, pitches from its strides.
+    Raises ValueError for a tensor the library cannot write in place."""
+    _, tdtype = rgb_dtype({v: k for k, v in _abi.RGB_DTYPES.items()}[code])
+    w, h = rgb_tensor_size(out, layout)
+    check_rgb_size(w, h)
+    if out.dtype != tdtype:
+        raise ValueError(f'out has dtype {out.dtype}, the call asks for {tdtype}')
+    if out.shape[0] < nframes:
+        raise ValueError(f'out holds {out.shape[0]} frames, the call converts {nframes}')
+    E = _abi.RGB_ELEM_BYTES[code]
+    st = [int(v) for v in out.stride()]
+    if st[3] != 1:
+        raise ValueError(f'out needs an innermost stride of 1, got {st[3]}')
+    d = _abi.H2SRgbFrames()
+    if layout == 'chw':
+        frame, plane, row = st[0], st[1], st[2]
+        if row < w or plane < row * h:
+            raise ValueError(f'out has overlapping rows or planes (strides {st})')
+        extent = 3 * plane
+    else:
+        if st[2] != 3:
+            raise ValueError(f"layout 'hwc' needs stride(-2) == 3 (packed pixels), got {st[2]}")
+        frame, plane, row = st[0], 0, st[1]
+        if row < 3 * w:
+            raise ValueError(f'out has overlapping rows (strides {st})')
+        extent = row * h
+    if out.shape[0] == 1:
+        frame = max(frame, extent)      # (the stride of a dimension of size 1 says nothing)
+    if frame < extent:
+        raise ValueError(f'out has overlapping frames (strides {st})')
+    d.data = out.data_ptr()
+    d.width, d.height, d.dtype, d.layout = w, h, code, _abi.RGB_LAYOUTS[layout]
+    d.row_pitch, d.plane_pitch, d.frame_pitch = row * E, plane * E, frame * E
+    for k in range(3):
+        d.scale[k], d.bias[k] = scale[k], bias[k]
+    return d
+
+
 class Tonemapper:
     """One context per GPU / worker (contexts share no state)."""
 
@@ -212,6 +290,45 @@ class Tonemapper:
         di, do = src.descriptor(), dst.descriptor()
         self._check(self._L.h2s_process_scaled(self._ctx, ctypes.byref(di), ctypes.byref(do), int(n),
                                                self._stream_ptr(stream)))
+
+    def process_rgb(self, src: FrameBatch, out: Any = None, size: 'tuple[int, int] | None' = None,
+                    dtype: Any = 'uint8', layout: str = 'chw', mean: Any = None, std: Any = None,
+                    stream: Any = None, nframes: 'int | None' = None) -> Any:
+        """Tone-map src and deliver the SDR picture as an R'G'B' torch tensor
+        on the device (h2s_process_rgb): ``layout`` 'chw' gives N x 3 x H x W,
+        'hwc' N x H x W x 3, in ``dtype`` 'uint8' | 'float16' | 'bfloat16' |
+        'float32' (or the torch dtype).  uint8 holds 0..255; the float dtypes
+        hold 0..1, or ``(x - mean) / std`` per channel with ``mean`` / ``std``
+        (three floats each).  ``size=(w, h)`` resizes as process_scaled does
+        (even sizes, at most 12 : 1 per axis: a 4K source cannot go straight to
+        224 x 224).  ``out`` is written in place through its strides (innermost
+        stride 1, 'hwc' also stride(-2) == 3: a padded or sliced view works);
+        without it a tensor is allocated on the context's device.  The call is
+        queued on ``stream`` (default: torch's current stream), so the tensor
+        is safe for the next torch op on that stream."""
+        import torch
+        n = src.nframes if nframes is None else int(nframes)
+        if n > src.nframes:
+            raise ValueError(f'nframes {n} exceeds the batch ({src.nframes} in)')
+        code, tdtype = rgb_dtype(dtype)
+        if layout not in _abi.RGB_LAYOUTS:
+            raise ValueError(f"layout must be 'chw' or 'hwc', got {layout!r}")
+        scale, bias = rgb_normalisation(code, mean, std)
+        if out is None:
+            w, h = (src.width, src.height) if size is None else (int(size[0]), int(size[1]))
+            check_rgb_size(w, h)
+            device = src.buf.device if src.is_torch and src.buf.is_cuda else f'cuda:{self.device}'
+            out = torch.empty((n, 3, h, w) if layout == 'chw' else (n, h, w, 3), dtype=tdtype, device=device)
+        elif size is not None and tuple(int(v) for v in size) != rgb_tensor_size(out, layout):
+            raise ValueError(f'size {tuple(size)} is not the size of out {rgb_tensor_size(out, layout)}')
+        d = rgb_frames(out, code, layout, scale, bias, n)
+        if not out.is_cuda:
+            raise ValueError('out must be a tensor on the device (h2s_process_rgb writes device memory only)')
+        self._use_layouts(src)
+        di = src.descriptor()
+        self._check(self._L.h2s_process_rgb(self._ctx, ctypes.byref(di), ctypes.byref(d), n,
+                                            self._stream_ptr(stream)))
+        return out
 
     def __call__(self, src: FrameBatch, stream: Any = None, out_layout: str = 'planar',
                  size: 'tuple[int, int] | None' = None) -> FrameBatch:

@@ -471,6 +471,128 @@ class H2SProcess:
             p.kill()
 
 
+class RgbReader:
+    """Iterator over a planned source as R'G'B' tensors on the device: it runs
+    only the plan's decode pipe and yields ``tonemapper.process_rgb(...)`` of
+    each batch of decoded frames (the last one short), in decode order.  For a
+    torch pipeline on the same card, a thumbnail or storyboard writer, a QC
+    tool: no encoder, no second pass on the CPU.
+
+    ``rgb_kw`` goes to ``Tonemapper.process_rgb`` (dtype, layout, mean, std,
+    size, stream); a plan with a ``scale=`` box delivers that size unless
+    ``size`` says otherwise.  Each yielded tensor is a fresh allocation unless
+    ``out`` is given, in which case the consumer must be done with it before
+    asking for the next batch.  The decode-side reader and its ``depth`` pinned
+    input slots are H2SProcess's: the decoder runs ahead while the consumer
+    works.  A slot is free again when process_rgb returns (a host batch is
+    staged before it does).
+
+    A decode failure (the child's non-zero exit) or a GPU error ends the
+    iteration with the error raised; the child is reaped on ``close()`` and on
+    exhaustion.  Also a context manager."""
+
+    def __init__(self, plan: PipePlan, tonemapper: Any, batch: int = 8, depth: int = 2,
+                 popen: Callable[..., Any] = subprocess.Popen, **rgb_kw: Any):
+        from .frames import FrameBatch
+        self.plan = plan
+        self.error: Optional[BaseException] = None
+        self.frames = 0
+        self._tm = tonemapper
+        self._batch = max(1, int(batch))
+        self._kw = dict(rgb_kw)
+        if plan.scaled and 'size' not in self._kw and 'out' not in self._kw:
+            self._kw['size'] = (plan.out_width, plan.out_height)
+        self._closed = False
+        self.dec = popen(plan.decode, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, stdin=subprocess.DEVNULL)
+        # (as H2SProcess: the libplacebo branch's 4:2:0 front-end, off for every other plan)
+        if plan.decimate == 'gpu':
+            tonemapper.set_input_decimation('bicubic')
+        elif hasattr(tonemapper, 'set_input_decimation'):
+            tonemapper.set_input_decimation('off')
+        p = plan.params
+        self._src = [FrameBatch.empty_pinned(self._batch, plan.width, plan.height, p.bits_in, plan.in_layout,
+                                             plan.in_subsampling, plan.in_range, plan.in_chroma_location)
+                     for _ in range(max(1, int(depth)))]
+        self._free: 'queue.Queue[Optional[int]]' = queue.Queue()
+        self._filled: 'queue.Queue[Optional[Tuple[int, int]]]' = queue.Queue()
+        for i in range(len(self._src)):
+            self._free.put(i)
+        self._reader = threading.Thread(target=self._read, name='h2s-rgb-read', daemon=True)
+        self._reader.start()
+
+    _read = H2SProcess._read      # decoder pipe -> free input slots, in order
+
+    def _fail(self, e: BaseException) -> None:
+        if self.error is None:
+            self.error = e
+        try:
+            self.dec.kill()
+        except Exception:
+            pass
+
+    def __iter__(self) -> 'RgbReader':
+        return self
+
+    def __next__(self) -> Any:
+        if self._closed:
+            raise StopIteration
+        item = self._filled.get()
+        if item is None:               # the decoder's pipe ended (or the reader failed)
+            self._shutdown(kill=False)
+            if self.error is not None:
+                raise self.error
+            if self.dec.returncode not in (0, None):
+                self.error = RuntimeError(f'the decode pipe failed with exit code {self.dec.returncode}')
+                raise self.error
+            raise StopIteration
+        slot, n = item
+        try:
+            if self.plan.dovi is not None:   # this batch's records (frames self.frames .. + n)
+                from .dovi import resolve_records
+                self._tm.set_dovi(resolve_records(self.plan.dovi, self.frames, n))
+            out = self._tm.process_rgb(self._src[slot], nframes=n, **self._kw)
+        except BaseException as e:
+            self._fail(e)
+            self.close()
+            raise
+        self._free.put(slot)
+        self.frames += n
+        return out
+
+    def close(self) -> None:
+        """Stop the reader and reap the decode child (idempotent)."""
+        self._shutdown(kill=True)
+
+    def _shutdown(self, kill: bool) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        self._free.put(None)           # release a reader waiting for a slot
+        if kill and self.dec.poll() is None:
+            try:
+                self.dec.kill()        # (closed early: the reader may be blocked on the pipe)
+            except Exception:
+                pass
+        self._reader.join()
+        self.dec.wait()
+        try:
+            self.dec.stdout.close()
+        except Exception:
+            pass
+
+    def __enter__(self) -> 'RgbReader':
+        return self
+
+    def __exit__(self, *exc: Any) -> None:
+        self.close()
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def start(plan: PipePlan, device: int = 0, batch: int = 8, lattice: 'np.ndarray | None' = None,
           popen: Callable[..., Any] = subprocess.Popen) -> H2SProcess:
     """Launch a planned conversion on ``device`` (the GPU replacement of

@@ -67,7 +67,9 @@ extern "C" {
  * h2s_set_dovi (Dolby Vision profile 5: per-frame RPU records);
  * h2s_scaled_size / h2s_process_scaled (convert and downscale in one call:
  * scaled 4:2:0 output); h2s_set_input_decimation (a 4:2:2 / 4:4:4 source
- * decimated to 4:2:0 on the device in front of either pipeline).  No existing
+ * decimated to 4:2:0 on the device in front of either pipeline);
+ * h2s_process_rgb (the converted frames as an R'G'B' tensor on the device:
+ * u8 / half / bfloat16 / float32, HWC or CHW, normalised).  No existing
  * struct, signature or default behaviour changes, so the symbol's presence in
  * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -783,6 +785,73 @@ int h2s_preview_source_rgb24_batch(h2s_ctx *ctx, const h2s_frames *in, int nfram
 int h2s_scaled_size(int in_w, int in_h, int box_w, int box_h, int *out_w, int *out_h);
 int h2s_process_scaled(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *out,
                        int nframes, void *hip_stream);
+
+/* ---- RGB tensor output: the converted frames as R'G'B' on the device -------
+ * [EXT], parity unpinned like the rest of the preview tail.
+ * h2s_process_rgb is h2s_process when out has the source's size and
+ * h2s_process_scaled when the sizes differ, either followed by a
+ * Y'CbCr -> R'G'B' stage on the chain's quantised 4:2:0 codes.  Everything in
+ * front is untouched: both pipelines, peak_detect, Dolby Vision records, input
+ * layouts, subsampling, tags and decimation.
+ *   Let q be the chain's quantising depth (8 in H2S_MODE_COMPAT8, bits_out in
+ *   H2S_MODE_NATIVE and on the libplacebo branch at gamma 1) and s = 2^(q-8).
+ *   The codes y, u, v are what h2s_process / h2s_process_scaled would write,
+ *   >> (bits_out - q).  Pixel (x, y) takes the chroma sample (x>>1, y>>1):
+ *   nearest, as h2s_preview_rgb24 does.  In float32, with the preview's BT.709
+ *   limited-range constants and operation order:
+ *     Y = 1.16438356f * ((float)y - 16 s)   U = (float)u - 128 s   V = (float)v - 128 s
+ *     cR = fmaf(1.79274107f, V, Y)
+ *     cG = fmaf(-0.53290933f, V, fmaf(-0.21324861f, U, Y))
+ *     cB = fmaf(2.11240179f, U, Y)
+ *   - H2S_RGB_U8: floor(c * (1/s) + 0.5) clamped to [0, 255] (the product is
+ *     exact).  At q = 8 this is h2s_preview_rgb24 at display gamma 1,
+ *     operation for operation.
+ *   - H2S_RGB_F32 / _F16 / _BF16: v = min(max(c * inv, 0), 1) with
+ *     inv = (float)(1 / (255 s)); out_k = fmaf(scale[k], v, bias[k]), stored
+ *     as float32 or rounded to nearest-even to half / bfloat16.  For an
+ *     (x/255 - mean) / std normalisation: scale = 1/std, bias = -mean/std.
+ *   No display gamma is applied.
+ * Layouts: H2S_RGB_HWC interleaves R, G, B (a pixel is 3 elements, a row
+ * 3 * width); H2S_RGB_CHW writes three planes plane_pitch bytes apart.  Every
+ * pitch is in bytes and a multiple of the element size; data is aligned to the
+ * element size.  Rows that start at multiples of 16 bytes (data and every
+ * pitch used) are written with 16-byte stores, others element by element, to
+ * the same values.
+ * `in` is validated as h2s_process validates it and may be device or host
+ * memory; the output is device memory only.  With a device input the call is
+ * asynchronous on hip_stream.  With a host input the frames are staged as
+ * h2s_process stages them and the call returns once that is done; the RGB
+ * kernel is then still queued on hip_stream, so the consumer must be ordered
+ * after that stream (or synchronise it) either way.
+ * The size rules and limits are h2s_process_scaled's: width and height even
+ * and >= 2, source / target <= 12 per axis and target <= 4 * 8192, else
+ * H2S_E_UNSUPPORTED: a 3840x2160 -> 224x224 request is refused (17 : 1), such
+ * a consumer resizes a 320x180 output further itself.  Batches longer than 16
+ * frames run in chunks, stream-ordered, in the scaled output's scratch and
+ * with its cached tap tables: a steady-state call makes no host -> device copy
+ * and no synchronisation.  With h2s_set_timing the record gains one entry per
+ * chunk for the RGB launch, after the chunk's conversion entry and, if the
+ * sizes differ, its resize entry.
+ * H2S_E_INVALID_ARG: NULL ctx / in / out / out->data; params not set;
+ * nframes < 0; an odd or non-positive target size; an unknown dtype or layout;
+ * H2S_RGB_U8 with a scale != 1 or a bias != 0; a non-finite scale or bias; a
+ * pitch that is not a multiple of the element size; row_pitch smaller than one
+ * row; CHW plane_pitch < row_pitch * height; frame_pitch smaller than one
+ * frame's extent (HWC: row_pitch * height; CHW: 3 * plane_pitch); data not
+ * aligned to the element size. */
+enum h2s_rgb_dtype  { H2S_RGB_U8 = 0, H2S_RGB_F16 = 1, H2S_RGB_BF16 = 2, H2S_RGB_F32 = 3 };
+enum h2s_rgb_layout { H2S_RGB_HWC = 0, H2S_RGB_CHW = 1 };
+typedef struct h2s_rgb_frames {
+  void   *data;                 /* device memory */
+  int32_t width, height;        /* target size; even, >= 2 */
+  int32_t dtype, layout;        /* enum h2s_rgb_dtype, enum h2s_rgb_layout */
+  int64_t row_pitch;            /* bytes between rows */
+  int64_t plane_pitch;          /* CHW: bytes between the R, G, B planes; HWC: ignored */
+  int64_t frame_pitch;          /* bytes between frames */
+  float   scale[3], bias[3];    /* float dtypes; U8 requires (1,1,1) / (0,0,0) */
+} h2s_rgb_frames;
+int h2s_process_rgb(h2s_ctx *ctx, const h2s_frames *in, const h2s_rgb_frames *out,
+                    int nframes, void *hip_stream);
 
 /* ---- .cube helpers (tools/generate_lut.py:28-119; lut3d's .cube parser) --
  * h2s_cube_generate: the BT.2020->BT.709 lattice, n^3 triples, .cube order,
