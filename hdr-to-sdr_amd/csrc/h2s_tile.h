@@ -27,6 +27,12 @@
 // 16-byte loads; then, in 8 steps, each wave processes one dense 8 x 8 pixel
 // sub-block with one pixel per lane (lanes 4q..4q+3 = one 2x2 quad).  Dense
 // sub-blocks keep the 64 lanes of every lattice gather on few cache lines;
+// in a step the block's four waves take the four quarters of one 16 x 16
+// macro-block (8 macro-blocks per tile, walked row by row), so the gathers the
+// CU has in flight from one block share lattice lines in the L1 (the CPU
+// chain's instances; the libplacebo instances, which gather nothing from the
+// lattice, keep a 16-pixel column strip per wave: DESIGN.md §4.1, "Wave
+// layout"; scripts/l1_wave_layout_sim.py);
 // chroma is reduced per quad with DPP quad permutes and all outputs leave
 // through LDS as 16-byte coalesced stores.  Measured balance (DESIGN.md
 // §4.1): VALU ~70 % busy, LDS ~47 %, vector-memory return ~35 %.
@@ -182,15 +188,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
       pqi_lds[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rpi, 16 * i, 0, 0));
   }
 
-  // ---- per-lane step geometry: wave w, step s -> 8x8 sub-block
-  // (2w + (s&1), s>>1); lane = pixel (quad q = lane>>2 in a 4x4 quad grid,
-  // position lane&3 in the quad) ----
+  // ---- per-lane step geometry: step m is the 16x16 macro-block (m & 3,
+  // m >> 2) of the tile, of which wave w takes the 8x8 quarter (w & 1, w >> 1),
+  // i.e. sub-block (2 (m&3) + (w&1), 2 (m>>2) + (w>>1)); lane = pixel (quad
+  // q = lane>>2 in a 4x4 quad grid, position lane&3 in the quad).  The wave's
+  // quarter goes into the per-lane bases below, the step into compile-time
+  // LDS offsets (16 columns per m & 3, 16 rows per m >> 2).  One LDS
+  // instruction still covers 8 rows x 8 columns from one base, and the wave's
+  // quarter shifts that base by whole 8-sample chunks and whole groups of 8
+  // luma (4 chroma) rows: the bank arguments at luma_at, row_stride, C422_ST
+  // and C444_ST hold for every wave as they held for the strips ----
+  // MB: the macro-block layout above, every CPU-chain instance.  The
+  // libplacebo instances (LP) keep the layout this kernel had before it: wave w
+  // walks the 16-pixel column strip w, step s = sub-block (2w + (s&1), s>>1).
+  // Their rgba8 download rounds a value that float32 carries to about 1e-4 of
+  // a code, and moving an 8x8 block to another unrolled step moved one such
+  // tie of one instance's output ("Wave layout"): their bytes
+  // stay what they were
+  constexpr bool MB = !LP;
+  auto SX = [](int s) { return MB ? 16 * (s & 3) : 8 * (s & 1); };    // step s's pixel offset from step 0's
+  auto SY = [](int s) { return MB ? 16 * (s >> 2) : 8 * (s >> 1); };
+  const int wx = MB ? w & 1 : 2 * w, wy = MB ? __builtin_amdgcn_readfirstlane(w >> 1) : 0;   // the wave's first sub-block
   const int qx = (lane >> 2) & 3, qy = lane >> 4, pxl = lane & 1, pyl = (lane >> 1) & 1;
-  const int xl = 16 * w + 2 * qx + pxl, yl = 2 * qy + pyl;           // step (0,0) pixel
-  uint16_t* ybase = reinterpret_cast<uint16_t*>(yin + luma_at(xl, yl));   // this lane's sample of step (0, 0)
+  const int xl = 8 * wx + 2 * qx + pxl, yl = 8 * wy + 2 * qy + pyl;   // step 0's pixel (MB: (x, y) mod 16 at every step)
+  uint16_t* ybase = reinterpret_cast<uint16_t*>(yin + luma_at(xl, yl));   // this lane's sample of step 0
   // vertical pass (centre siting): 3 x row cy + row cy-1 (top) / cy+1 (bottom)
-  const float* h0 = hrow[0] + (qy + 1) * HST + xl;
-  const float* h1 = hrow[1] + (qy + 1) * HST + xl;
+  const float* h0 = hrow[0] + ((yl >> 1) + 1) * HST + xl;
+  const float* h1 = hrow[1] + ((yl >> 1) + 1) * HST + xl;
   // (SUB 3, rows co-sited with the even luma row: row cy again (even luma rows) / cy+1 (odd))
   const int hb = SUB == 3 ? (pyl ? HST : 0) : (pyl ? HST : -HST);
   // SUB 1: the pixel's own chroma row, sample xl >> 1 and (odd columns) the one right of it
@@ -199,7 +223,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
   // SUB 2: the pixel's own sample
   const int16_t* s0 = reinterpret_cast<const int16_t*>(hrow[0]) + yl * C444_ST + xl;
   const int16_t* s1 = reinterpret_cast<const int16_t*>(hrow[1]) + yl * C444_ST + xl;
-  float* csb = csum[0] + qy * CBW + 8 * w + qx;
+  float* csb = csum[0] + csum_at(xl >> 1, yl >> 1);   // the quad's chroma sample of step 0
 
   // hot constants live in VGPRs for the whole kernel.  Staged samples:
   // luma Y*ys + y_off (+1 on PQ: pq_z's zero segment), chroma centred on its
@@ -222,12 +246,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
                 LP ? in_vgpr(F.lp_k1) : 0.0f};
   gu32* lut8v = LP ? in_vgpr64(F.lut8x) : nullptr;   // (a 64-bit VGPR base: no SGPRs to spill)
   // libplacebo branch: the rgba8 download offset of this lane's pixel at step
-  // s (x mod 16 = xl + 8 (s & 1), y mod 16 = yl + 8 ((s >> 1) & 1): tile
-  // origins are multiples of 16)
+  // s (x mod 16 = xl + SX(s), y mod 16 = yl + SY(s) mod 16: tile origins are
+  // multiples of 16; the strips' four positions are steps 0..3's)
   float qo[4];
 #pragma unroll
   for (int i = 0; i < 4; i++)
-    qo[i] = LP ? F.lp_qo + (F.lp_dith ? bayer16(xl + 8 * (i & 1), yl + 8 * (i >> 1)) : 0.5f) -
+    qo[i] = LP ? F.lp_qo + (F.lp_dith ? bayer16(xl + SX(i), yl + SY(i)) : 0.5f) -
                      (F.lut_off ? 0.0f : F.lp_k2 * F.lp_qs_f)
                : 0.5f;
 
@@ -261,24 +285,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
       cv.sp_srcmax = in_vgpr(cv.sp_srcmax), cv.sp_umax = in_vgpr(cv.sp_umax);
     }
     const __amdgpu_buffer_rsrc_t lut = __builtin_amdgcn_make_buffer_rsrc((void*)F.lut_yuv, (short)0, F.lut_bytes, 0x00020000);
-    // A step pair whose 8 rows lie past the frame's last row computes what is
-    // never stored (the bottom tile row of a 2160-row frame: steps 4-7), so it
-    // is skipped: block-uniform, product instances, not the BICUBIC scratch
-    // path.  Only this exact-capable body tests for it (k_tile sends such
-    // tiles here), so the fast body stays one straight-line block
-    const int live = !FB && DBG == 0 && !F.chr444 ? F.H - g.py0 : TBH;   // the tile's rows inside the frame
+    // A wave's sub-block whose 8 rows lie past the frame's last row computes
+    // what is never stored, so it is skipped.  Macro-blocks: on the bottom tile
+    // row of a 2160-row frame (16 live rows) that is macro-row 1, steps 4-7,
+    // for every wave; with 8 or 24 live rows also the lower waves' quarters of
+    // the last live macro-row.  Strips: whole step pairs.  The test is
+    // wave-uniform (no barrier sits inside the steps) and applies to product
+    // instances, not to the BICUBIC scratch path.  Only this exact-capable body
+    // tests for it (k_tile sends such tiles here), so the fast body stays one
+    // straight-line block
+    // (live: the frame's rows from the first row of this wave's step-0 sub-block on)
+    const int live = !FB && DBG == 0 && !F.chr444 ? F.H - g.py0 - 8 * wy : TBH;
     // the 2x2 chroma sums of step s (or, BICUBIC, the pixel's Cb, Cr into the
     // frame's 4:4:4 scratch, which k_chroma_bicubic decimates; the scratch
     // has whole tiles of rows: rows past F.H are written, never read)
     auto chroma_out = [&](int s, float oyv, float ozv) {
       if (!FB && F.chr444) {
-        const int px = g.px0 + xl + 8 * (s & 1), py = g.py0 + yl + 8 * (s >> 1);
+        const int px = g.px0 + xl + SX(s), py = g.py0 + yl + SY(s);
         F.chr444[(long long)py * F.chr_w + px] = make_float2(oyv * F.inv_c56, ozv * F.inv_c56);
         return;
       }
       // chroma: 2x2 sums; the 4 lanes of a quad store the same value
       H2S_MARK("S6 chroma quad sums");
-      const int oc = 4 * (s >> 1) * CBW + 4 * (s & 1);
+      const int oc = csum_at(SX(s) / 2, SY(s) / 2);   // (MB: whole 256-byte units, csum_at)
       const float su = quad_sum(oyv), sv = quad_sum(ozv);
       csb[oc] = su;
       csb[oc + CBH * CBW] = sv;
@@ -295,9 +324,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
 #pragma unroll
         for (int s = 0; s <= 8; s++) {
           unsigned vn = 0;
-          if (s < 8 && (FB || 8 * (s >> 1) < live)) {
-            const int oy = 8 * (s >> 1) * YR2 + 8 * (s & 1);
-            const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
+          // (the bottom-tile skip: the same wave-uniform condition on step s
+          // here and on step s - 1 below, so what is issued is finished)
+          if (s < 8 && (FB || SY(s) < live)) {
+            const int oy = SY(s) * YR2 + SX(s);
+            const int oh = SY(s) / 2 * HST + SX(s);
             H2S_MARK("S0 step: staged Y, vertical chroma");
             const float ybs = fmaf((float)ybase[oy], ysc, yoff);
             // x8 upsampled, centred, exact (SUB 3: 4 h[cy], or 2 (h[cy] + h[cy+1]))
@@ -309,14 +340,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
             H2S_MARK("S3 encode");
             vn = lp_table_read(F, K, lut8v, spread_lds, r, gg, bl, qo[s & 3]);
           }
-          if (s > 0 && (FB || 8 * ((s - 1) >> 1) < live)) {
+          if (s > 0 && (FB || SY(s - 1) < live)) {
             const int sp = s - 1;
             const float R8 = (float)(vp & 255u), G8 = (float)((vp >> 8) & 255u), B8 = (float)((vp >> 16) & 255u);
             H2S_MARK("S5 Y'CbCr");
             const f3 o = lp_ycbcr(F, K, R8, G8, B8);
             H2S_MARK("S7 eq");
             // luma code (eq applied, shifted) replaces the luma sample this lane read
-            ybase[8 * (sp >> 1) * YR2 + 8 * (sp & 1)] = eq_lds[(int)o.x];
+            ybase[SY(sp) * YR2 + SX(sp)] = eq_lds[(int)o.x];
             chroma_out(sp, o.y, o.z);
           }
           vp = vn;
@@ -327,17 +358,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
     }
 #pragma unroll
     for (int s = 0; s < 8; s++) {
-      if (!FB && (s & 1) == 0 && 8 * (s >> 1) >= live) break;
-      const int oy = 8 * (s >> 1) * YR2 + 8 * (s & 1);   // compile-time LDS offsets
-      const int oh = 4 * (s >> 1) * HST + 8 * (s & 1);
+      if (!FB && SX(s) == 0 && SY(s) >= live) break;   // (wave-uniform)
+      const int oy = SY(s) * YR2 + SX(s);   // compile-time LDS offsets
+      const int oh = SY(s) / 2 * HST + SX(s);
       H2S_MARK("S0 step: staged Y, vertical chroma");
       const float ybs = fmaf((float)ybase[oy], ysc, yoff);   // (the staged luma: Y*ys + y_off, +1 on PQ)
       float U, V;
       if constexpr (SUB == 1) {   // 4 h at the pixel's row: 8 c[k], or 4 (c[k] + c[k+1])
-        const int oc = 8 * (s >> 1) * C422_ST + 4 * (s & 1);
+        const int oc = SY(s) * C422_ST + SX(s) / 2;
         U = 4.0f * (c0[oc] + c0[oc + pxl]), V = 4.0f * (c1[oc] + c1[oc + pxl]);
       } else if constexpr (SUB == 2) {   // 8 (code - mid)
-        const int oc = 8 * (s >> 1) * C444_ST + 8 * (s & 1);
+        const int oc = SY(s) * C444_ST + SX(s);
         U = 8.0f * (float)s0[oc], V = 8.0f * (float)s1[oc];
       } else if constexpr (SUB == 3) {   // 4 h[cy] (even luma rows), or 2 (h[cy] + h[cy+1])
         U = 2.0f * (h0[oh] + h0[oh + hb]), V = 2.0f * (h1[oh] + h1[oh + hb]);
@@ -345,8 +376,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LP ? TILE_W
         U = fmaf(3.0f, h0[oh], h0[oh + hb]);   // x8 upsampled, centred, exact
         V = fmaf(3.0f, h1[oh], h1[oh + hb]);
       }
-      const long long di = DBG && g.f == 0 && g.py0 + yl + 8 * (s >> 1) < F.H
-                               ? (long long)(g.py0 + yl + 8 * (s >> 1)) * F.dbg_w + g.px0 + xl + 8 * (s & 1)
+      const long long di = DBG && g.f == 0 && g.py0 + yl + SY(s) < F.H
+                               ? (long long)(g.py0 + yl + SY(s)) * F.dbg_w + g.px0 + xl + SX(s)
                                : -1;
       float oyv, ozv;
       // luma code (eq applied, shifted) replaces the luma sample this lane read

@@ -12,6 +12,21 @@
 namespace h2s {
 
 constexpr int CBW = 32, CBH = 16;  // chroma tile
+// The 2x2 chroma sums in LDS (csum, one plane of CBH * CBW floats each for Cb
+// and Cr): sample (cx, cy) of the chroma tile at float csum_at(cx, cy), laid
+// out by macro-column (8 chroma columns = one 16-pixel macro-block column of
+// k_tile's steps), then row, then column.  A step's offset from the wave's
+// per-lane base (macro-column: 512 bytes, macro-row: 8 rows = 256 bytes) and
+// the plane stride (2048 bytes) are then all multiples of 256 bytes, the unit
+// of the offsets of the one ds_write2st64_b32 that stores both sums, so every
+// step writes from the same base register.  The 4 rows x 4 columns a wave
+// writes per step lie 8 floats apart per row: 16 distinct banks, no conflict.
+// The store phase reads a row's 8-sample chunk (one macro-column) as 32
+// contiguous bytes
+constexpr int csum_at(int cx, int cy) { return (cx >> 3) * (CBH * 8) + cy * 8 + (cx & 7); }
+static_assert(csum_at(8, 0) * 4 % 256 == 0 && csum_at(0, 8) * 4 % 256 == 0 && CBH * CBW * 4 % 256 == 0,
+              "a step's and the plane's offsets are whole 256-byte units");
+static_assert(csum_at(CBW - 1, CBH - 1) == CBH * CBW - 1, "csum_at fills the plane");
 // LDS row stride (floats) of the horizontally upsampled chroma rows (and, until
 // the luma tile became 16-bit codes at its own stride, luma_at, of the staged
 // luma floats: the measurements below are of both).  72 on the CPU chain's instances: a step's 8 rows x 8
@@ -390,7 +405,7 @@ __device__ __forceinline__ void put_luma(const FastParams& F, const TileGeo& g, 
 // chroma plane pl, row r, chunk c (8 samples): ((c0 + c1) + (c2 + c3)) + bias,
 // quantised once per sample, packed as read_luma
 __device__ __forceinline__ u4v read_chroma(const FastParams& F, const float* csum, int pl, int r, int c) {
-  const float4* src = reinterpret_cast<const float4*>(csum + pl * (CBH * CBW) + r * CBW + 8 * c);
+  const float4* src = reinterpret_cast<const float4*>(csum + pl * (CBH * CBW) + csum_at(8 * c, r));
   const float4 v0 = src[0], v1 = src[1];
   const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
   unsigned code[8];
@@ -425,8 +440,8 @@ __device__ __forceinline__ void put_chroma(const FastParams& F, const TileGeo& g
 // 8 chunks, quantised as read_chroma, packed as pairs for one 16-byte store
 // (u16: the code in the word's high bits, F.out_sh) or 8-byte store (nv12: .xy)
 __device__ __forceinline__ u4v read_chroma_semi(const FastParams& F, const float* csum, int r, int c) {
-  const float4 vu = *reinterpret_cast<const float4*>(csum + r * CBW + 4 * c);
-  const float4 vv = *reinterpret_cast<const float4*>(csum + CBH * CBW + r * CBW + 4 * c);
+  const float4 vu = *reinterpret_cast<const float4*>(csum + csum_at(4 * c, r));
+  const float4 vv = *reinterpret_cast<const float4*>(csum + CBH * CBW + csum_at(4 * c, r));
   const float s[8] = {vu.x, vv.x, vu.y, vv.y, vu.z, vv.z, vu.w, vv.w};
   unsigned code[8];
   if (F.dither) {   // sample (cx, cy) mod 8 = (4 (c & 1) + k / 2, r mod 8)
