@@ -965,6 +965,10 @@ int h2s_set_option(h2s_ctx* c, int key, int64_t value) {
       if (value != c->scale_taps.uploads)
         return fail(c, H2S_E_INVALID_ARG, "scaled-output tap uploads: " + std::to_string(c->scale_taps.uploads));
       return 0;
+    case H2S_OPT_TEST_LADDER_UPLOADS:
+      if (value != c->ladder_uploads)
+        return fail(c, H2S_E_INVALID_ARG, "ladder tap uploads: " + std::to_string(c->ladder_uploads));
+      return 0;
     case H2S_OPT_TEST_PEAK_CHUNK:
       if (value < 0 || value > 4096) return fail(c, H2S_E_INVALID_ARG, "peak chunk must be in [0, 4096]");
       c->peak_chunk = (int)value;

@@ -40,7 +40,10 @@ h2s_frames scratch_frames(int W, int H, int bits, uint8_t* base) {
 // key rewrites them: the launches that read the old ones are waited for first
 // (Scratch::reserve's rule, h2s_api_preview.hip)
 int ensure_taps(h2s_ctx* c, int W, int H, int ow, int oh, hipStream_t s) {
-  ScaleTaps& t = c->scale_taps;
+  return fill_taps(c, c->scale_taps, W, H, ow, oh, s);
+}
+
+int fill_taps(h2s_ctx* c, ScaleTaps& t, int W, int H, int ow, int oh, hipStream_t s) {
   if (t.W == W && t.H == H && t.ow == ow && t.oh == oh) return 0;
   if (t.d_w) {
     drain_launches(c);
@@ -110,25 +113,26 @@ int fill_plane(h2s_ctx* c, ScalePlane* L, const ScaleTaps& t, int ax, int ay, in
   return fail(c, H2S_E_UNSUPPORTED, "scaled output: one output row's taps exceed the kernel's LDS budget");
 }
 
+}  // namespace
+
+namespace h2s {
+namespace host {
+
 bool rows_aligned16(const h2s_frames* f, Format fmt) {
   for (int p = 0; p < fmt.planes(); p++)
     if ((uintptr_t)f->data[p] % 16 || f->linesize[p] % 16 || f->frame_pitch[p] % 16) return false;
   return true;
 }
 
-}  // namespace
-
-namespace h2s {
-namespace host {
-
-// the launch of one chunk: mid (the chain's frames) -> dout
-int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int nf, Format out_fmt, hipStream_t s) {
+// the launch record of one chunk: mid (the chain's frames) -> dout
+int scale_record(h2s_ctx* c, const ScaleTaps& t, const h2s_frames* mid, const h2s_frames* dout, Format out_fmt,
+                 ScaleParams* Pout) {
   KParams g{};   // the two sets as the conversion kernels bind them (semi-planar: plane 2 aliases plane 1)
-  fill_geometry(&g, mid, dout, nf, PLANAR_420, out_fmt);
-  const ScaleTaps& t = c->scale_taps;
+  fill_geometry(&g, mid, dout, 1, PLANAR_420, out_fmt);
   const int src_bps = mid->bits == 8 ? 1 : 2, out_bps = dout->bits == 8 ? 1 : 2;
   const int W = mid->width, H = mid->height, ow = dout->width, oh = dout->height;
-  ScaleParams P{};
+  ScaleParams& P = *Pout;
+  P = ScaleParams{};
   P.nplanes = out_fmt.planes();
   int rc;
   if ((rc = fill_plane(c, &P.pl[0], t, ScaleTaps::X, ScaleTaps::Y, W, H, ow, oh, 1, src_bps, out_bps))) return rc;
@@ -146,10 +150,22 @@ int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int 
   P.shift_out = c->k.shift_out, P.rep_rs = c->k.expand_rep && c->k.shift_out ? 8 - c->k.shift_out : 31;
   P.out_sh = g.out_sh, P.out_bps = out_bps;
   P.vec_out = rows_aligned16(dout, out_fmt) ? 1 : 0;
+  return 0;
+}
+
+int launch_scale(h2s_ctx* c, const ScaleParams& P0, int src_bps, int dst_f0, int nf, hipStream_t s) {
+  ScaleParams P = P0;
+  for (int e = 0; e < P.nplanes; e++) P.pl[e].dst += (long long)dst_f0 * P.pl[e].dfp;
   timing_begin(c, s);
   const hipError_t e = h2s::launch_scale420(P, src_bps, nf, s);
   timing_end(c, s);
   return e == hipSuccess ? 0 : hip_fail(c, e, "scale kernel launch");
+}
+
+int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int nf, Format out_fmt, hipStream_t s) {
+  ScaleParams P;
+  if (int rc = scale_record(c, c->scale_taps, mid, dout, out_fmt, &P)) return rc;
+  return launch_scale(c, P, mid->bits == 8 ? 1 : 2, 0, nf, s);
 }
 
 }  // namespace host

@@ -10,6 +10,7 @@
 //   h2s_api_scale.hip    the scaled 4:2:0 output (h2s_process_scaled)
 //   h2s_api_decimate.hip the 4:2:0 front-end of a 4:2:2 / 4:4:4 set (h2s_set_input_decimation)
 //   h2s_api_rgb.hip      the RGB tensor output (h2s_process_rgb)
+//   h2s_api_ladder.hip   a rendition ladder from one conversion (h2s_process_ladder)
 //
 // Everything declared here has hidden visibility: the library's dynamic
 // symbols are the h2s_* calls of include/h2s.h and nothing else.
@@ -281,6 +282,12 @@ struct h2s_ctx {
   h2s::host::Dev<uint8_t> d_scale;
   h2s::host::ScaleTaps scale_taps;
   h2s::host::Ordered scale_use;             // after the last scaled call (d_scale and the tables in use)
+  // a rendition ladder (h2s_process_ladder): its own tap tables, one entry per
+  // (W, H, ow, oh) of a scaled rung; scale_taps and its upload count stay
+  // h2s_process_scaled's.  d_scale and scale_use serve the ladder too
+  h2s::host::ScaleTaps ladder_taps[H2S_LADDER_MAX];
+  long long ladder_uploads = 0;             // (H2S_OPT_TEST_LADDER_UPLOADS)
+  unsigned ladder_evict = 0;                // the entry a new size replaces next when every one holds a size
   // the 4:2:0 front-end (h2s_set_input_decimation): a host chunk's staged
   // source frames, then the decimated chroma of one chunk
   int decimate = H2S_DECIMATE_OFF;
@@ -406,11 +413,20 @@ int decimate_end(h2s_ctx* c, hipStream_t s);
 int process_decimated(h2s_ctx* c, const h2s_frames* in, const h2s_frames* out, int nframes, hipStream_t s,
                       Format in_fmt, Format out_fmt, int dovi_f0);
 
-// ---- h2s_api_scale.hip (shared with h2s_api_rgb.hip) ----
+// ---- h2s_api_scale.hip (shared with h2s_api_rgb.hip and h2s_api_ladder.hip) ----
 
 constexpr int kChunk = 16;   // frames of the scaled output's scratch at the most
 h2s_frames scratch_frames(int W, int H, int bits, uint8_t* base);
+bool rows_aligned16(const h2s_frames* f, Format fmt);
+// the tables of one cache entry: t is c->scale_taps (ensure_taps) or one of c->ladder_taps
+int fill_taps(h2s_ctx* c, ScaleTaps& t, int W, int H, int ow, int oh, hipStream_t s);
 int ensure_taps(h2s_ctx* c, int W, int H, int ow, int oh, hipStream_t s);
+// the resize of one chunk, mid -> dout with t's tables: the launch record
+// (every choice of the host's, no HIP call), then its launch over nf frames
+// whose destination starts dst_f0 frames into dout
+int scale_record(h2s_ctx* c, const ScaleTaps& t, const h2s_frames* mid, const h2s_frames* dout, Format out_fmt,
+                 ScaleParams* P);
+int launch_scale(h2s_ctx* c, const ScaleParams& P, int src_bps, int dst_f0, int nf, hipStream_t s);
 int launch_chunk(h2s_ctx* c, const h2s_frames* mid, const h2s_frames* dout, int nf, Format out_fmt, hipStream_t s);
 
 // ---- h2s_api_dovi.hip ----

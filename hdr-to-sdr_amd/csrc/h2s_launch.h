@@ -1,6 +1,6 @@
 // h2s_launch.h — the one declaration of every host-callable kernel launcher.
 // Included by the unit that defines a launcher (h2s_kernels.hip, h2s_peak.hip,
-// h2s_fast.hip, h2s_preview.hip, h2s_scale.hip, h2s_decimate.hip, h2s_rgb.hip) and by every unit that calls one (the host
+// h2s_fast.hip, h2s_preview.hip, h2s_scale.hip, h2s_decimate.hip, h2s_rgb.hip, h2s_repack.hip) and by every unit that calls one (the host
 // units, h2s_testhooks.hip), so a signature or an
 // enum value that drifts apart is a compile error, not a misrouted launch.
 #pragma once
@@ -20,6 +20,7 @@ struct SrcPreviewParams;  // h2s_srcprev.h
 struct ScaleParams;       // h2s_scale.h
 struct DecimateParams;    // h2s_decimate.h
 struct RgbParams;         // h2s_rgb.h
+struct RepackParams;      // h2s_repack.h
 
 // launch_process's form: PF_VEC the rows allow vector accesses, PF_OUT8 8-bit
 // output, PF_C444 BICUBIC chroma pass 1 (luma + per-pixel chroma into P.chr444)
@@ -66,5 +67,9 @@ hipError_t launch_decimate420(const DecimateParams& P, int sub, bool semi, int n
 // h2s_rgb.hip: nframes planar 4:2:0 scratch frames to R'G'B' in one launch (src_bps: bytes of a scratch sample;
 // dtype, layout: enum h2s_rgb_dtype, enum h2s_rgb_layout); it fills P's run and row-pair counts
 hipError_t launch_rgb420(const RgbParams& P, int src_bps, int dtype, int layout, int nframes, hipStream_t s);
+
+// h2s_repack.hip: every plane of nframes planar 4:2:0 scratch frames copied into a planar or semi-planar set of the
+// same size in one launch (bps: bytes of a sample on both sides); it fills P's chunk and block counts
+hipError_t launch_repack420(const RepackParams& P, int bps, bool semi, int nframes, hipStream_t s);
 
 }  // namespace h2s

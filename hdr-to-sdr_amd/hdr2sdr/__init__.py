@@ -11,7 +11,8 @@ from .dovi import DoviCurve, DoviRpu  # noqa: F401
 from .engine import Tonemapper  # noqa: F401
 from .frames import FrameBatch, frame_bytes  # noqa: F401
 from .lut import LUT_SIZE, cube_text, generate_cube_lines, generate_lattice, load_cube, parse_cube  # noqa: F401
-from .plan import H2SProcess, PipePlan, RgbReader, plan_from_argv, scaled_size  # noqa: F401
+from .plan import (H2SLadderProcess, H2SProcess, LadderPlan, PipePlan, RgbReader,  # noqa: F401
+                   plan_from_argv, plan_ladder, scaled_size)
 from .preview import PREVIEW_SIZE, Previewer, fit_size, source_box  # noqa: F401
 
 __all__ = [
@@ -20,5 +21,5 @@ __all__ = [
     'frame_bytes', 'LUT_SIZE', 'cube_text', 'generate_cube_lines', 'generate_lattice',
     'load_cube', 'parse_cube', 'H2SError', 'lib', 'H2SProcess', 'PipePlan', 'plan_from_argv',
     'PREVIEW_SIZE', 'Previewer', 'fit_size', 'source_box', 'DoviCurve', 'DoviRpu', 'scaled_size',
-    'RgbReader',
+    'RgbReader', 'H2SLadderProcess', 'LadderPlan', 'plan_ladder',
 ]

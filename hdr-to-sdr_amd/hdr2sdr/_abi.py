@@ -60,6 +60,8 @@ OPT_RESERVED_PRIVATE_2 = 0x7f000000 + 2   # was OPT_TEST_PEAK_FORM: now INVALID_
 OPT_TEST_PEAK_CHUNK = 0x7f000000 + 3
 OPT_TEST_PEAK_BLOCKS = 0x7f000000 + 4
 OPT_TEST_SCALE_UPLOADS = 0x7f000000 + 5   # a query: OK when the scaled output's tap uploads equal the value
+OPT_TEST_LADDER_UPLOADS = 0x7f000000 + 6   # the same query for h2s_process_ladder's own tap tables
+LADDER_MAX = 8   # H2S_LADDER_MAX: rungs of one h2s_process_ladder call at the most
 PATH_TILE, PATH_TILE_TAIL, PATH_GENERIC, PATH_TWO_PASS = 1, 2, 3, 4
 ABI_VERSION = 3
 ABI_MINOR = 4   # include/h2s.h H2S_ABI_MINOR (the loaded library may be newer, not older)
@@ -74,6 +76,7 @@ EXPORTS = (
     'h2s_set_frame_layout', 'h2s_set_input_subsampling', 'h2s_set_input_tags',
     'h2s_preview_source_rgb24', 'h2s_preview_source_rgb24_batch', 'h2s_set_dovi',
     'h2s_scaled_size', 'h2s_process_scaled', 'h2s_set_input_decimation', 'h2s_process_rgb',
+    'h2s_process_ladder',
 )
 RGB_U8, RGB_F16, RGB_BF16, RGB_F32 = 0, 1, 2, 3   # enum h2s_rgb_dtype (h2s_process_rgb)
 RGB_DTYPES = {'uint8': RGB_U8, 'float16': RGB_F16, 'bfloat16': RGB_BF16, 'float32': RGB_F32}
@@ -245,6 +248,9 @@ def lib() -> ctypes.CDLL:
                                               ctypes.c_int, ctypes.c_void_p]),
         'h2s_process_rgb': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SRgbFrames),
                                            ctypes.c_int, ctypes.c_void_p]),
+        # (outs: an array of H2SFrames, one per rung)
+        'h2s_process_ladder': (ctypes.c_int, [c_ctx, ctypes.POINTER(H2SFrames), ctypes.POINTER(H2SFrames),
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

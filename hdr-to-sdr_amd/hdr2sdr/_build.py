@@ -27,9 +27,9 @@ SOURCES = ['h2s_kernels.hip', 'h2s_debug_lp_dv_semi.hip', 'h2s_debug_lp_dv.hip',
            'h2s_fast_sub422.hip', 'h2s_fast.hip', 'h2s_fast_sub444.hip', 'h2s_peak.hip', 'h2s_api.hip',
            'h2s_resolve.hip', 'h2s_api_peak.hip', 'h2s_api_preview.hip', 'h2s_api_dovi.hip', 'h2s_preview.hip',
            'h2s_scale.hip', 'h2s_api_scale.hip', 'h2s_decimate.hip', 'h2s_api_decimate.hip',
-           'h2s_rgb.hip', 'h2s_api_rgb.hip', 'h2s_testhooks.hip', 'h2s_cube.cpp']
+           'h2s_rgb.hip', 'h2s_api_rgb.hip', 'h2s_repack.hip', 'h2s_api_ladder.hip', 'h2s_testhooks.hip', 'h2s_cube.cpp']
 HEADERS = ['h2s_params.h', 'h2s_math.h', 'h2s_chain.h', 'h2s_tile.h', 'h2s_tile_tone.h', 'h2s_tile_px.h', 'h2s_tile_io.h', 'h2s_tile_sets.h',
-           'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_dovi.h', 'h2s_srcprev.h', 'h2s_scale.h', 'h2s_decimate.h', 'h2s_rgb.h', 'h2s_launch.h', 'h2s_host.h']
+           'h2s_peak.h', 'h2s_libm.h', 'h2s_lpx.h', 'h2s_dovi.h', 'h2s_srcprev.h', 'h2s_scale.h', 'h2s_decimate.h', 'h2s_rgb.h', 'h2s_repack.h', 'h2s_launch.h', 'h2s_host.h']
 
 
 def _hipcc() -> str:

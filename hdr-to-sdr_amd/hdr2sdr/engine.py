@@ -8,7 +8,7 @@ the fused HIP kernel over whole batches of device-resident frames.
 from __future__ import annotations
 
 import ctypes
-from typing import Any
+from typing import Any, Sequence
 
 import numpy as np
 
@@ -94,6 +94,13 @@ def rgb_frames(out: Any, code: int, layout: str, scale: Any, bias: Any, nframes:
     for k in range(3):
         d.scale[k], d.bias[k] = scale[k], bias[k]
     return d
+
+
+def _residence(batch: Any) -> str:
+    """'host', or the torch device of a batch's buffer (Tonemapper.process_ladder)."""
+    buf = getattr(batch, 'buf', None)
+    dev = getattr(buf, 'device', None)
+    return 'host' if dev is None or getattr(dev, 'type', 'cpu') == 'cpu' else str(dev)
 
 
 class Tonemapper:
@@ -290,6 +297,60 @@ class Tonemapper:
         di, do = src.descriptor(), dst.descriptor()
         self._check(self._L.h2s_process_scaled(self._ctx, ctypes.byref(di), ctypes.byref(do), int(n),
                                                self._stream_ptr(stream)))
+
+    def process_ladder(self, src: FrameBatch, dsts: 'Sequence[FrameBatch]', nframes: 'int | None' = None,
+                       stream: Any = None) -> None:
+        """Tone-map src once and write every rung of a rendition ladder
+        (h2s_process_ladder): ``dsts`` is one to ``_abi.LADDER_MAX``
+        destination batches, each of its own width x height (the source's size
+        is a rung too), all of one layout, bit depth and residence (all numpy,
+        or all torch tensors on one device).  Each rung's bytes are those of
+        ``process_scaled`` (``process`` for a rung of the source's size) on an
+        equal context, but every frame is converted, and counted by the dynamic
+        peak, once.  Asynchronous when every batch is on the device.  The
+        arguments are checked here (ValueError) before the library is called."""
+        dsts = list(dsts)
+        if not 1 <= len(dsts) <= _abi.LADDER_MAX:
+            raise ValueError(f'a ladder has 1 to {_abi.LADDER_MAX} rungs, got {len(dsts)}')
+        n = src.nframes if nframes is None else int(nframes)
+        if n < 0:
+            raise ValueError(f'nframes {n} is negative')
+        for i, d in enumerate(dsts):
+            if n > src.nframes or n > d.nframes:
+                raise ValueError(f'rung {i}: nframes {n} exceeds the batch ({src.nframes} in, {d.nframes} out)')
+            if d.width < 2 or d.height < 2 or d.width % 2 or d.height % 2:
+                raise ValueError(f'rung {i}: the target needs even width and height >= 2, got {d.width}x{d.height}')
+            if getattr(d, 'subsampling', '420') != '420':
+                raise ValueError(f'rung {i}: the output side is 4:2:0 (destination batch subsampling must be 420)')
+            for what in ('layout', 'bits'):
+                a, b = getattr(d, what, None), getattr(dsts[0], what, None)
+                if a != b:
+                    raise ValueError(f'rung {i}: {what} {a!r} differs from rung 0 ({b!r})')
+            if _residence(d) != _residence(dsts[0]):
+                raise ValueError(f'rung {i}: every rung must live where rung 0 does '
+                                 f'({_residence(d)} != {_residence(dsts[0])})')
+        self._use_layouts(src, dsts[0])
+        di = src.descriptor()
+        outs = (_abi.H2SFrames * len(dsts))(*[d.descriptor() for d in dsts])
+        self._check(self._L.h2s_process_ladder(self._ctx, ctypes.byref(di), outs, len(dsts), n,
+                                               self._stream_ptr(stream)))
+
+    def ladder(self, src: FrameBatch, sizes: 'Sequence[tuple[int, int]]', stream: Any = None,
+               out_layout: str = 'planar') -> 'list[FrameBatch]':
+        """The converted batch at every ``(w, h)`` of ``sizes``, each allocated
+        beside src as ``tm(src, size=(w, h))`` allocates it, from one conversion
+        (process_ladder)."""
+        if self.params is None:
+            raise ValueError('set_params first')
+        dsts = []
+        for w, h in sizes:
+            if src.is_torch:
+                dsts.append(FrameBatch.empty_torch(src.nframes, int(w), int(h), self.params.bits_out,
+                                                   src.buf.device, out_layout))
+            else:
+                dsts.append(FrameBatch.empty_numpy(src.nframes, int(w), int(h), self.params.bits_out, out_layout))
+        self.process_ladder(src, dsts, stream=stream)
+        return dsts
 
     def process_rgb(self, src: FrameBatch, out: Any = None, size: 'tuple[int, int] | None' = None,
                     dtype: Any = 'uint8', layout: str = 'chw', mean: Any = None, std: Any = None,

@@ -593,6 +593,191 @@ class RgbReader:
             pass
 
 
+@dataclass
+class LadderPlan:
+    """A rendition ladder from one source: ``rungs[i]`` is the PipePlan of
+    rung i (its own encode argv, output path and size), ``decode`` the one
+    decode argv they share."""
+    rungs: 'list[PipePlan]'
+    decode: 'list[str]'
+
+    @property
+    def params(self) -> TonemapParams:
+        return self.rungs[0].params
+
+    @property
+    def lut_path(self) -> 'str | None':
+        return self.rungs[0].lut_path
+
+    @property
+    def frame_bytes_in(self) -> int:
+        return self.rungs[0].frame_bytes_in
+
+    @property
+    def sizes(self) -> 'list[Tuple[int, int]]':
+        return [(r.out_width, r.out_height) for r in self.rungs]
+
+
+# what every rung of a ladder must agree on: one decoder, one conversion
+_LADDER_SHARED = ('input_path', 'decode', 'params', 'lut_path', 'width', 'height', 'in_layout', 'layout',
+                  'in_subsampling', 'in_range', 'in_chroma_location', 'decimate')
+
+
+def plan_ladder(argvs: 'list[list[str]]', properties: 'dict[str, Any]',
+                boxes: 'list[Tuple[int, int] | None]', **kw: Any) -> LadderPlan:
+    """The plans of a rendition ladder (a 4K master as 2160p, 1080p, 720p and
+    360p SDR files) that one decoder and one conversion per frame serve.
+
+    ``argvs[i]`` is the reference's own ``build()`` argv for rung i (its own
+    output path and rate arguments), ``boxes[i]`` that rung's ``scale=`` box,
+    or None for the source's size; ``kw`` goes to ``plan_from_argv``
+    unchanged.  ``rungs[i]`` is ``plan_from_argv(argvs[i], properties,
+    scale=boxes[i], **kw)`` field for field.  The rungs must agree on the input
+    path, the decode argv, the parameters, the LUT path, the layouts and the
+    source's form (what one decode pipe and one ``Tonemapper.process_ladder``
+    call per batch can serve): a ValueError names the first rung and field
+    that differ from rung 0."""
+    argvs, boxes = list(argvs), list(boxes)
+    if not argvs:
+        raise ValueError('a ladder needs at least one rung')
+    if len(argvs) != len(boxes):
+        raise ValueError(f'{len(argvs)} argvs but {len(boxes)} boxes: one box (or None) per rung')
+    from . import _abi
+    if len(argvs) > _abi.LADDER_MAX:
+        raise ValueError(f'a ladder has at most {_abi.LADDER_MAX} rungs, got {len(argvs)}')
+    if 'scale' in kw:
+        raise ValueError('scale= is per rung: pass boxes')
+    rungs = [plan_from_argv(a, properties, scale=b, **kw) for a, b in zip(argvs, boxes)]
+    for i, r in enumerate(rungs[1:], 1):
+        for name in _LADDER_SHARED:
+            a, b = getattr(r, name), getattr(rungs[0], name)
+            if (repr(a) != repr(b)) if name == 'params' else (a != b):    # (params holds NaN defaults)
+                raise ValueError(f'rung {i}: {name} differs from rung 0 ({a!r} != {b!r})')
+    return LadderPlan(rungs=rungs, decode=list(rungs[0].decode))
+
+
+class H2SLadderProcess:
+    """Popen-shaped handle of a decode -> libh2s -> one encoder per rung
+    conversion: H2SProcess with several encode pipes.  One decoder feeds the
+    pinned input slots, each batch takes one ``process_ladder`` call, and each
+    rung's pinned batch is then written to its encoder's stdin, in rung order
+    (one writer thread per encoder is not built: a slow encoder holds the
+    others back).
+
+    ``stderr`` is rung 0's encoder's stderr as text lines (the others' are
+    discarded).  ``returncode`` is None while anything runs, then 1 when the
+    GPU stage raised (``error`` holds the exception), else the first non-zero
+    code among the encoders, in rung order, and the decoder, else 0."""
+
+    def __init__(self, plan: LadderPlan, tonemapper: Any, batch: int = 8,
+                 popen: Callable[..., Any] = subprocess.Popen, depth: int = 2):
+        from .frames import FrameBatch
+        self.plan = plan
+        self.error: Optional[BaseException] = None
+        self._tm = tonemapper
+        self._batch = max(1, int(batch))
+        first = plan.rungs[0]
+        self.dec = popen(plan.decode, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, stdin=subprocess.DEVNULL)
+        self.encs = [popen(r.encode, stdin=subprocess.PIPE, stdout=subprocess.DEVNULL,
+                           stderr=subprocess.PIPE if i == 0 else subprocess.DEVNULL)
+                     for i, r in enumerate(plan.rungs)]
+        self.stderr = io.TextIOWrapper(self.encs[0].stderr, encoding='utf-8', errors='replace')
+        p = plan.params
+        # (as H2SProcess: the libplacebo branch's 4:2:0 front-end, off for every other plan)
+        if first.decimate == 'gpu':
+            tonemapper.set_input_decimation('bicubic')
+        elif hasattr(tonemapper, 'set_input_decimation'):
+            tonemapper.set_input_decimation('off')
+        self._src = [FrameBatch.empty_pinned(self._batch, first.width, first.height, p.bits_in, first.in_layout,
+                                             first.in_subsampling, first.in_range, first.in_chroma_location)
+                     for _ in range(max(1, int(depth)))]
+        self._dsts = [FrameBatch.empty_pinned(self._batch, r.out_width, r.out_height, p.bits_out, r.layout)
+                      for r in plan.rungs]
+        self._free: 'queue.Queue[Optional[int]]' = queue.Queue()
+        self._filled: 'queue.Queue[Optional[Tuple[int, int]]]' = queue.Queue()
+        for i in range(len(self._src)):
+            self._free.put(i)
+        self.frames = 0
+        self._reader = threading.Thread(target=self._read, name='h2s-ladder-read', daemon=True)
+        self._thread = threading.Thread(target=self._pump, name='h2s-ladder-pump', daemon=True)
+        self._reader.start()
+        self._thread.start()
+
+    _read = H2SProcess._read      # decoder pipe -> free input slots, in order
+
+    def _fail(self, e: BaseException) -> None:
+        """GPU / pipe failure: record the first error and stop every process."""
+        if self.error is None:
+            self.error = e
+        for p in [self.dec] + self.encs:
+            try:
+                p.kill()
+            except Exception:
+                pass
+
+    def _pump(self) -> None:
+        """Filled slots -> libh2s -> every encoder pipe, in decode order."""
+        fouts = [r.frame_bytes_out for r in self.plan.rungs]
+        mvs = [memoryview(d.buf).cast('B') for d in self._dsts]
+        dovi = self.plan.rungs[0].dovi
+        try:
+            while True:
+                item = self._filled.get()
+                if item is None:
+                    break
+                slot, n = item
+                if dovi is not None:             # this batch's records (frames self.frames .. + n)
+                    from .dovi import resolve_records
+                    self._tm.set_dovi(resolve_records(dovi, self.frames, n))
+                self._tm.process_ladder(self._src[slot], self._dsts, nframes=n)   # synchronous for host frames
+                self._free.put(slot)
+                for enc, mv, fout in zip(self.encs, mvs, fouts):
+                    enc.stdin.write(mv[:n * fout])
+                self.frames += n
+        except BaseException as e:
+            self._fail(e)
+        finally:
+            self._free.put(None)          # release a reader waiting for a slot
+            for enc in self.encs:
+                try:
+                    enc.stdin.close()
+                except Exception:
+                    pass
+
+    # ---- Popen surface -----------------------------------------------------
+    @property
+    def returncode(self) -> 'int | None':
+        codes = [enc.poll() for enc in self.encs]
+        if any(rc is None for rc in codes) or self._thread.is_alive():
+            return None
+        if self.error is not None:
+            return 1
+        for rc in codes + [self.dec.poll()]:
+            if rc not in (None, 0):
+                return rc
+        return 0
+
+    def poll(self) -> 'int | None':
+        return self.returncode
+
+    def wait(self, timeout: 'float | None' = None) -> int:
+        self._thread.join(timeout)
+        self._reader.join(timeout)
+        for p in self.encs + [self.dec]:
+            p.wait(timeout)
+        rc = self.returncode
+        assert rc is not None
+        return rc
+
+    def terminate(self) -> None:
+        for p in [self.dec] + self.encs:
+            p.terminate()
+
+    def kill(self) -> None:
+        for p in [self.dec] + self.encs:
+            p.kill()
+
+
 def start(plan: PipePlan, device: int = 0, batch: int = 8, lattice: 'np.ndarray | None' = None,
           popen: Callable[..., Any] = subprocess.Popen) -> H2SProcess:
     """Launch a planned conversion on ``device`` (the GPU replacement of

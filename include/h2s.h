@@ -69,7 +69,9 @@ extern "C" {
  * scaled 4:2:0 output); h2s_set_input_decimation (a 4:2:2 / 4:4:4 source
  * decimated to 4:2:0 on the device in front of either pipeline);
  * h2s_process_rgb (the converted frames as an R'G'B' tensor on the device:
- * u8 / half / bfloat16 / float32, HWC or CHW, normalised).  No existing
+ * u8 / half / bfloat16 / float32, HWC or CHW, normalised);
+ * h2s_process_ladder (a rendition ladder, several sizes of the 4:2:0 output,
+ * from one conversion of each frame).  No existing
  * struct, signature or default behaviour changes, so the symbol's presence in
  * the loaded library is the feature test. */
 #define H2S_ABI_MINOR 4
@@ -273,6 +275,9 @@ enum h2s_option {
  * tap tables exactly `value` times, else H2S_E_INVALID_ARG (the count is in
  * h2s_last_error) */
 #define H2S_OPT_TEST_SCALE_UPLOADS (H2S_OPT_PRIVATE_BASE + 5)
+/* the same query for h2s_process_ladder's own tap tables (one upload per
+ * distinct rung size; h2s_process_scaled's count is not touched by a ladder) */
+#define H2S_OPT_TEST_LADDER_UPLOADS (H2S_OPT_PRIVATE_BASE + 6)
 #endif
 
 /* Kernel path h2s_process takes for a given frame pair (h2s_query_path). */
@@ -852,6 +857,48 @@ typedef struct h2s_rgb_frames {
 } h2s_rgb_frames;
 int h2s_process_rgb(h2s_ctx *ctx, const h2s_frames *in, const h2s_rgb_frames *out,
                     int nframes, void *hip_stream);
+
+/* ---- rendition ladder: several sizes of the 4:2:0 output from one conversion
+ * [EXT], like h2s_process_scaled.  A transcode box delivers a ladder from each
+ * master (2160p, 1080p, 720p, 360p).  h2s_process_ladder writes outs[0 ..
+ * n_outs - 1], each a frame set as h2s_process_scaled takes one: its width x
+ * height are the rung's size, its depth is params.bits_out, its layout the
+ * context's output layout, its pitches its own.  The rungs may come in any
+ * order, may repeat a size and may have the source's own size; all of them
+ * share one location.
+ *   Per chunk of at most 16 frames the chain runs ONCE, as h2s_process_scaled
+ *   runs it, into the context's full-size planar scratch, and every rung is
+ *   made from that scratch on hip_stream, in rung order: a smaller (or larger)
+ *   rung by h2s_process_scaled's resize, arithmetic and limits; a rung of the
+ *   source's size by a copy of the finished codes into its layout and pitches.
+ *   So a source frame is converted exactly once, the dynamic peak's state
+ *   (params.peak_detect) advances by nframes whatever n_outs is and every rung
+ *   is tone-mapped with one curve, and Dolby Vision record f belongs to frame
+ *   f of the call.  Each rung's bytes are those of the separate call on an
+ *   equal context: h2s_process_scaled for a scaled rung; for a source-size
+ *   rung h2s_process into a set whose rows start at multiples of 16 bytes (the
+ *   scratch's form, which decides the kernel route).
+ *   n_outs == 1: the call is h2s_process_scaled(ctx, in, &outs[0], ...) and
+ *   nothing else.
+ * Every input option of h2s_process_scaled carries over (semi-planar, 4:2:2 /
+ * 4:4:4 and host input, input tags, input decimation).  Device rungs are
+ * asynchronous on hip_stream; host rungs are staged in the scratch behind the
+ * intermediate and the call returns after the stream has finished.  The
+ * ladder keeps tap tables of its own, up to H2S_LADDER_MAX sizes per context,
+ * uploaded once each: a steady-state call makes no host -> device copy and no
+ * synchronisation (a ninth size replaces one, after a wait for the context's
+ * queued launches); h2s_process_scaled's cached tables are not touched.  With
+ * h2s_set_timing a chunk records its conversion entry, then one entry per
+ * rung in rung order.
+ * H2S_E_INVALID_ARG: NULL ctx / in / outs; n_outs < 1 or > H2S_LADDER_MAX; a
+ * rung with an odd or non-positive size, a NULL plane, the wrong depth or a
+ * short pitch; rungs of differing location.  H2S_E_UNSUPPORTED: a rung beyond
+ * h2s_process_scaled's limits (source / target > 12 on an axis, target >
+ * 4 * 8192).  The message names the rung's index.  A refused call has queued
+ * nothing, written no rung and left the peak state as it was. */
+#define H2S_LADDER_MAX 8
+int h2s_process_ladder(h2s_ctx *ctx, const h2s_frames *in, const h2s_frames *outs,
+                       int n_outs, int nframes, void *hip_stream);
 
 /* ---- .cube helpers (tools/generate_lut.py:28-119; lut3d's .cube parser) --
  * h2s_cube_generate: the BT.2020->BT.709 lattice, n^3 triples, .cube order,
